@@ -9,15 +9,27 @@ HBM. The headline workload (BASELINE.json configs[1]) is Bunny primary rays at
 (rays counted / kernel time, App.cc:204). Scenes are deterministic synthetic
 stand-ins with the published triangle counts (the OBJ assets are absent).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--extra/--no-extra]
-                  [--readme-cells default|all|none] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+                  [--full [--extra/--no-extra] [--readme-cells default|all|none]] [--scaling weak|strong]
+
+A plain run does what the line's figure needs and no more: it builds (or loads) the
+workload's BVH, generates its rays, warms up, times the K steps and prints the line
+(value, ms_per_step and the configuration; at N > 1 the strong-scaling measurement,
+which is that line's value). --dump-outputs DIR also writes the {id, t} results the
+last timed step left, as DIR/batch<b>_hit_id.npy (float64) and DIR/batch<b>_hit_t.npy
+(float32): scenes, rays and the exact-reciprocal closest hits are deterministic, so two
+builds can be compared output for output. Everything else is behind --full: the
+roofline and per-launch kernel time, the CPU baseline and the oracle's agreement, the
+fast-reciprocal mode, the autotuner's exploration cost, the extra workloads, the other
+README cells, strong scaling at N = 1 and the detail file. The descriptions below of
+what a run measures beside the headline are of a --full run.
 
 Multi-GPU (one rank per GPU, RCCL): under torch.distributed.run (WORLD_SIZE set)
 every process is one rank; `python bench.py --gpus N` without a launcher starts
 its N ranks itself as child processes before any GPU call (launch_ranks), relays
 rank 0's line and exits non-zero if any rank failed. Rank 0 builds the
 SBVH and broadcasts the Compact2 buffers, which stay in HBM (the BVH is
-replicated). Two scalings are measured in every run:
+replicated). Two scalings are measured in every --full run:
 
   * strong (BASELINE configs[4]; the line's value at N > 1): ONE
     fixed RayBuffer — hairball diffuse 1920x1080 x 8 spp = 16.6 M rays, generated
@@ -67,6 +79,7 @@ PROFILE_TAGS = ("round6", "round5", "round4")   # committed rocprofv3 summaries 
 PROFILE_RATIO = (0.9, 1.1)   # a cited profile's mean kernel time / this run's event time must lie in here
 LATENCY_BOUND = 0.25         # every memory level served below this fraction of its ceiling: bound = "latency"
 LINE_MAX_BYTES = 10_000  # the driver parses one stdout line; round 3's 21.7 kB line was not parsed
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much (a seeded sample of the rays above it)
 STORE = None             # mrt.schedules.ScheduleStore the tracer's schedules are locked from (main())
 LEARNED = None           # ScheduleStore collecting the schedules this run settled (--save-schedules)
 
@@ -365,10 +378,13 @@ class SceneCache:
             else:
                 bvh = mrt.Bvh.build(scene)
                 if path:
-                    os.makedirs(self.cache_dir, exist_ok=True)
-                    tmp = f"{path}.{os.getpid()}.tmp"
-                    bvh.save(tmp)
-                    os.replace(tmp, path)
+                    try:   # (a cache directory another user owns: the run goes on without saving)
+                        os.makedirs(self.cache_dir, exist_ok=True)
+                        tmp = f"{path}.{os.getpid()}.tmp"
+                        bvh.save(tmp)
+                        os.replace(tmp, path)
+                    except (OSError, RuntimeError) as err:
+                        log(f"[bvh-cache] {path} not written: {err}")
             bufs, stats = bvh.buffers(), bvh.stats()
             del bvh
         build_s = time.perf_counter() - t0
@@ -545,12 +561,13 @@ def warm(launches, warmup, min_seconds=0.3):
     return done
 
 
-def time_steps(launches, steps, warmup, world):
+def time_steps(launches, steps, warmup, world, probe=True, dump=None):
     """Warmup, then exactly `steps` steps bracketed by barrier + synchronize; wall
     time of the K steps (a multi-stream step is joined: see joined()). Then a probe
     pass: the average launch duration, from one HIP event pair on the launch stream
     around back-to-back launches (several streams: every launch bracketed by its own
-    pair, one at a time)."""
+    pair, one at a time). probe=False (a plain run) stops after the timed steps and
+    returns None for the launch duration."""
     import torch
     warmed = warm(launches, warmup)
     torch.cuda.synchronize()
@@ -564,6 +581,10 @@ def time_steps(launches, steps, warmup, world):
     barrier(world)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if dump is not None:   # the last timed step's results, before the probe's launches write them again
+        dump()
+    if not probe:
+        return wall, None, warmed
     probe = max(3, min(steps, 50))
     one_stream = all(go.stream == launches[0].stream for go in launches)
     if one_stream:
@@ -864,14 +885,61 @@ def readme_cell(name, tracer, scenes, steps, warmup, exact, want_cpu):
     return out
 
 
-def run_workload(name, tracer, scenes, world, rank, steps, warmup, exact, want_cpu, explore=False, fast=False):
+def dump_outputs(dirname, batches):
+    """--dump-outputs: what the timed launches left in each batch's RayResult array after the
+    last timed step — the {id, t} a caller of trace_batch reads — as <dirname>/batch<b>_hit_id.npy
+    (float64: the triangle index, -1 for a miss) and batch<b>_hit_t.npy (float32), in ray order.
+    Above DUMP_MAX_BYTES in all, every batch keeps the same fraction of its rays: a sorted sample
+    drawn without replacement from a generator seeded with the batch number, so two runs with the
+    same arguments write the same rays. Returns the files written."""
+    os.makedirs(dirname, exist_ok=True)
+    per_ray = 8 + 4
+    total = sum(rb.size for rb, _ in batches)
+    keep = (DUMP_MAX_BYTES - 256 * 2 * len(batches)) // per_ray   # (room for the .npy headers)
+    written = []
+    for b, (rb, _) in enumerate(batches):
+        res = rb.results_numpy()
+        if total > keep:
+            idx = np.sort(np.random.RandomState(b).choice(rb.size, size=rb.size * keep // total, replace=False))
+            res = res[idx]
+        for name, arr in ((f"batch{b}_hit_id", res[:, 0].astype(np.float64)),
+                          (f"batch{b}_hit_t", np.ascontiguousarray(res[:, 1]).view(np.float32))):
+            np.save(os.path.join(dirname, name + ".npy"), arr)
+            written.append(name + ".npy")
+    return written
+
+
+def run_headline(name, tracer, scenes, world, rank, steps, warmup, exact, dump_dir=None):
+    """A plain run's workload: set up, warm up, time the steps, write the outputs when asked.
+    The fields make_line reads, and nothing that needs launches of its own (--full: run_workload)."""
+    scene_name = workload_spec(name)[0]
+    e = scenes.get(scene_name)
+    batches = Batches(name, e["scene"], e["gbvh"], tracer, rank)
+    launches = [tracer.launcher(rb, exact_rcp=exact) for rb, _ in batches.batches]
+    wall, _, warmed = time_steps(launches, steps, warmup, world, probe=False)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, batches.batches)
+    if LEARNED is not None:
+        LEARNED.update(e["gbvh"].fingerprint, tracer.schedules())
+    wall = reduce_over_ranks(wall, world)
+    counted = int(reduce_over_ranks(batches.rays_counted, world, "sum"))
+    return {"workload": name, "value": round(counted * steps / wall / 1e6, 2),
+            "ms_per_step": round(1e3 * wall / steps, 4), "kernel_ms_per_launch": None, "warmup_steps_run": warmed,
+            "rays_counted": batches.rays_counted, "rays_traced": batches.rays_traced,
+            "rays_counted_all_ranks": counted, "gather": None, "scene_tris": e["scene"].num_triangles,
+            "schedule": None, "roofline": None, "reference_mrays": REFERENCE_MRAYS.get(name)}
+
+
+def run_workload(name, tracer, scenes, world, rank, steps, warmup, exact, want_cpu, explore=False, fast=False,
+                 dump_dir=None):
     scene_name = workload_spec(name)[0]
     e = scenes.get(scene_name)
     batches = Batches(name, e["scene"], e["gbvh"], tracer, rank)
     alg_bytes, n_nodes, n_tris, n_leaves = algorithmic_bytes(tracer, batches.batches)
     k_bytes, k_nodes, k_tris = kernel_bytes(tracer, batches.batches)
     launches = [tracer.launcher(rb, exact_rcp=exact) for rb, _ in batches.batches]
-    wall, launch_ms, warmed = time_steps(launches, steps, warmup, world)
+    wall, launch_ms, warmed = time_steps(launches, steps, warmup, world, dump=(
+        (lambda: dump_outputs(dump_dir, batches.batches)) if dump_dir and rank == 0 else None))
     wall = reduce_over_ranks(wall, world)
     launch_ms = reduce_over_ranks(launch_ms, world)
     counted = int(reduce_over_ranks(batches.rays_counted, world, "sum"))
@@ -1384,6 +1452,15 @@ def main():
                                                              "(merged into the --tune-db store; tools/tune_db.sh)")
     ap.add_argument("--no-explore", action="store_true", help="skip measuring the autotuner's exploration cost")
     ap.add_argument("--no-fast", action="store_true", help="skip the fast-reciprocal (v_rcp_f32) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: its roofline, per-launch kernel time and schedule, "
+                         "the CPU baseline and oracle parity, the fast-reciprocal mode, the autotuner's exploration "
+                         "cost, the extra workloads and README cells, strong scaling at N=1 and the detail file "
+                         "(the --extra/--no-*/--readme-cells options choose among these). Without it a run sets "
+                         "up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps of --workload, write the {id, t} results its last step left "
+                         "(rank 0's batches) as DIR/batch<b>_hit_id.npy and DIR/batch<b>_hit_t.npy")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: this process starts the ranks and only waits (no GPU call here)
@@ -1419,16 +1496,20 @@ def main():
     if cfg:
         tracer.set_config(**cfg)
     exact = args.rcp == "exact"
-    want_cpu = (rank == 0 and world == 1 and not args.no_cpu)
+    want_cpu = (args.full and rank == 0 and world == 1 and not args.no_cpu)
     scenes = SceneCache(world, rank, args.bvh_cache or None)
 
     explore = want_cpu and not args.no_explore and not args.no_autotune
     fast = want_cpu and exact and not args.no_fast
-    head = run_workload(args.workload, tracer, scenes, world, rank, args.steps, args.warmup, exact, want_cpu,
-                        explore, fast)
+    if args.full:
+        head = run_workload(args.workload, tracer, scenes, world, rank, args.steps, args.warmup, exact, want_cpu,
+                            explore, fast, dump_dir=args.dump_outputs)
+    else:
+        head = run_headline(args.workload, tracer, scenes, world, rank, args.steps, args.warmup, exact,
+                            dump_dir=args.dump_outputs)
     log(f"[head] {args.workload}: {head['value']} Mrays/s")
     extras = []
-    do_extra = args.extra if args.extra is not None else (world == 1)
+    do_extra = args.full and (args.extra if args.extra is not None else (world == 1))
     if do_extra:
         for name in EXTRA_N1:
             if name != args.workload:
@@ -1444,7 +1525,7 @@ def main():
         cells.append(c)
         log(f"[readme] {name}: {c['value']} Mrays/s ({c['x_readme']}x README, agree {c.get('agree')})")
     strong = None
-    if not args.no_strong or args.scaling == "strong":
+    if (args.full and not args.no_strong) or args.scaling == "strong":   # (the line's own figure at N > 1)
         STRONG["min_launches"] = max(1, args.strong_min_launches)
         STRONG["block"] = max(0, args.strong_block)
         STRONG["streams"] = args.strong_streams
@@ -1454,14 +1535,17 @@ def main():
         STRONG["w"], STRONG["h"], STRONG["spp"] = (int(v) for v in args.strong_size.split("x"))
         STRONG["name"] = f"{STRONG['scene']}-diffuse-{STRONG['w']}x{STRONG['h']}x{STRONG['spp']}spp"
         strong = strong_scaling(tracer, scenes, world, rank, args.strong_steps, 3, exact,
-                                with_roofline=args.scaling == "strong")
+                                with_roofline=args.full and args.scaling == "strong")
         log(f"[strong] {strong['workload']} n={world}: T1 {strong['t1_ms']} ms, Tn {strong['tn_ms']} ms, "
             f"eta {strong['eta']} (with gather {strong['eta_with_gather']}); projected from one GPU: "
             f"{ {k: v['eta'] for k, v in (strong['projected_from_one_gpu'] or {}).items()} }")
 
     if rank == 0:
         line, detail = make_line(args, world, head, extras, strong, tracer.config(), cells)
-        if args.detail_out:
+        line["full"] = bool(args.full)
+        if args.dump_outputs:
+            line["outputs_dir"] = args.dump_outputs
+        if args.full and args.detail_out:
             os.makedirs(os.path.dirname(os.path.abspath(args.detail_out)), exist_ok=True)
             with open(args.detail_out, "w") as f:
                 json.dump(detail, f, indent=1)

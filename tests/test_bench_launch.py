@@ -94,13 +94,44 @@ def test_bench_gpus2_without_launcher_and_gpu_fails_loudly():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_its_outputs(tmp_path):
+    """Without --full: one line with the figure and ms_per_step for exactly --steps steps, nothing
+    measured beside it, no detail file; --dump-outputs leaves the batch's {id, t} as .npy."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+           "--workload", "mori-primary-96x64", "--dump-outputs", str(out), "--bvh-cache", str(tmp_path / "cache"),
+           "--detail-out", str(tmp_path / "detail.json")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 7 and line["n_gpus"] == 1 and line["scaling"] == "weak"
+    assert line["metric"] == bench.METRIC and line["unit"] == "Mrays/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["value"] > 0 and line["ms_per_step"] > 0
+    # value = rays / step time (ms_per_step is rounded to 1e-4 ms: within 2 % for a step of 2.5 us or more)
+    assert abs(line["value"] - 96 * 64 / (line["ms_per_step"] * 1e-3) / 1e6) <= 0.02 * line["value"]
+    for k in ("roofline", "cpu_baseline", "strong_scaling", "rcp_fast", "readme_cells"):
+        assert line[k] is None, k
+    assert line["extra_workloads"] == [] and not os.path.exists(tmp_path / "detail.json")
+    assert sorted(os.listdir(out)) == ["batch0_hit_id.npy", "batch0_hit_t.npy"]
+    ids, t = np.load(out / "batch0_hit_id.npy"), np.load(out / "batch0_hit_t.npy")
+    assert ids.dtype == np.float64 and t.dtype == np.float32 and ids.shape == t.shape == (96 * 64,)
+    hit = ids >= 0
+    assert 0 < hit.sum() and np.all(ids[~hit] == -1) and np.all(ids == np.round(ids))
+    assert np.all(np.isfinite(t[hit])) and np.all(t[hit] > 0)
+
+
+@pytest.mark.gpu
 def test_bench_gpus2_without_launcher_prints_one_strong_line(tmp_path):
     """Two ranks on one MI355X (gloo; each rank's own HIP tracer), started by bench.py itself:
     one JSON line, strong scaling, gathered results equal to rank 0's single-GPU trace, the
     schedule label read back from the library. A small strong-scaling frame keeps it short."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--no-extra",
-           "--steps", "5", "--warmup", "2", "--strong-steps", "5", "--strong-scene", "sponza",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--full",
+           "--no-extra", "--steps", "5", "--warmup", "2", "--strong-steps", "5", "--strong-scene", "sponza",
            "--strong-size", "320x240x4", "--detail-out", str(tmp_path / "detail.json"),
            "--bvh-cache", str(tmp_path / "cache")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=420, env=env, cwd=REPO)

@@ -8,6 +8,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -81,6 +82,68 @@ def test_line_at_n_gt_1_is_the_strong_scaling_number(rec):
     assert line["weak_scaling"]["value"] == head["value"]
     assert line["strong_scaling"]["value_n1_same_run"] > 0
     assert len(json.dumps(line)) < 10_000
+
+
+def test_plain_run_line_keeps_the_headline_fields():
+    """A run without --full has only run_headline's fields: the line still carries the figure
+    (metric, value, unit, higher_is_better, dtype, ms_per_step) and names nothing it did not measure."""
+    head = {"workload": bench.HEADLINE, "value": 7000.0, "ms_per_step": 0.1123, "kernel_ms_per_launch": None,
+            "warmup_steps_run": 2700, "rays_counted": 786432, "rays_traced": 786432,
+            "rays_counted_all_ranks": 786432, "gather": None, "scene_tris": 69451, "schedule": None,
+            "roofline": None, "reference_mrays": None}
+    line, _ = bench.make_line(args_for("weak"), 1, head, [], None, {}, [])
+    text = json.dumps(line, separators=(",", ":"))
+    assert json.loads(text) == line and len(text) <= bench.LINE_MAX_BYTES
+    for k in CONTRACT:
+        assert k in line, k
+    assert line["metric"] == bench.METRIC and line["unit"] == "Mrays/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["value"] == 7000.0 and line["ms_per_step"] == 0.1123
+    assert line["steps"] == 200 and line["warmup"] == 20
+    for k in ("roofline", "cpu_baseline", "strong_scaling", "rcp_fast", "readme_cells"):
+        assert line[k] is None, k
+    assert line["extra_workloads"] == [] and line["parity"] == {}
+
+
+class _FakeBatch:
+    def __init__(self, n, seed):
+        r = np.random.RandomState(seed)
+        self.res = np.zeros((n, 4), np.int32)
+        self.res[:, 0] = r.randint(-1, 1 << 24, n)
+        self.res[:, 1] = r.rand(n).astype(np.float32).view(np.int32)
+        self.size = n
+
+    def results_numpy(self):
+        return self.res
+
+
+def test_dump_outputs_writes_id_and_t_per_batch(tmp_path):
+    batches = [(_FakeBatch(1000, 1), 1000), (_FakeBatch(37, 2), 30)]
+    names = bench.dump_outputs(str(tmp_path / "out"), batches)
+    assert sorted(names) == sorted(os.listdir(tmp_path / "out")) == [
+        "batch0_hit_id.npy", "batch0_hit_t.npy", "batch1_hit_id.npy", "batch1_hit_t.npy"]
+    for b, (fb, _) in enumerate(batches):
+        ids, t = np.load(tmp_path / "out" / f"batch{b}_hit_id.npy"), np.load(tmp_path / "out" / f"batch{b}_hit_t.npy")
+        assert ids.dtype == np.float64 and t.dtype == np.float32
+        assert np.array_equal(ids, fb.res[:, 0]) and np.array_equal(t.view(np.int32), fb.res[:, 1])
+
+
+def test_dump_outputs_samples_the_same_rays_above_the_limit(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8192)
+    batches = [(_FakeBatch(5000, 1), 5000), (_FakeBatch(1234, 2), 1000)]
+    bench.dump_outputs(str(tmp_path / "a"), batches)
+    bench.dump_outputs(str(tmp_path / "b"), batches)
+    total, kept = 0, []
+    for name in sorted(os.listdir(tmp_path / "a")):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+        total += os.path.getsize(tmp_path / "a" / name)
+        kept.append(len(a))
+    assert total <= 8192 and kept[0] == kept[1] and kept[2] == kept[3] and 0 < kept[2] < kept[0] < 5000
+    # the sample is a subset of the batch's rays, in ray order
+    ids = np.load(tmp_path / "a" / "batch0_hit_id.npy")
+    src = batches[0][0].res[:, 0]
+    pos = np.searchsorted(np.sort(src), ids)
+    assert np.array_equal(np.sort(src)[pos], ids)
 
 
 def test_readme_cells_ride_on_the_n1_line():

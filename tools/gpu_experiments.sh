@@ -64,14 +64,14 @@ for exp in "$@"; do
       cat $O/ab_wideq.txt ;;
     strong_launches)
       for ML in 1 2 3 4; do
-        timeout -k 10 300 python bench.py --no-extra --no-cpu --no-fast --no-explore --steps 20 --strong-min-launches $ML \
+        timeout -k 10 300 python bench.py --full --no-extra --no-cpu --no-fast --no-explore --steps 20 --strong-min-launches $ML \
           --detail-out $O/strong_ml$ML.json > $O/strong_ml$ML.out 2> $O/strong_ml$ML.err || fail "ml $ML" $O/strong_ml$ML.err
         echo "min_launches $ML: $(grep strong $O/strong_ml$ML.err)"
       done ;;
     strong_blocks)
       for BAL in ${BALANCE:-1 0}; do for B in ${BLOCKS:-16384 4096 1024 256}; do
         T=b${B}_bal$BAL
-        timeout -k 10 300 python bench.py --no-extra --no-cpu --no-fast --no-explore --steps 20 --strong-steps 20 --strong-block $B \
+        timeout -k 10 300 python bench.py --full --no-extra --no-cpu --no-fast --no-explore --steps 20 --strong-steps 20 --strong-block $B \
           --strong-balance $BAL --detail-out $O/strong_$T.json > $O/strong_$T.out 2> $O/strong_$T.err || fail $T $O/strong_$T.err
         python3 -c "
 import json; d=json.load(open('$O/strong_$T.json'))['strong']
@@ -231,7 +231,7 @@ print('block $B balance $BAL T1', d['t1_ms'], 'one-stream', d.get('one_stream_ms
       cat $O/ab_ao5.txt ;;
     r5_order)   # projected eta(2/4/8) with the shard blocks live-first (1) vs cost-first (2), three runs each
       for run in 1 2 3; do for OR in 1 2; do
-        timeout -k 10 400 python bench.py --no-extra --no-cpu --no-explore --no-fast --steps 5 --strong-order $OR \
+        timeout -k 10 400 python bench.py --full --no-extra --no-cpu --no-explore --no-fast --steps 5 --strong-order $OR \
           --detail-out $O/order${OR}_$run.json > $O/order${OR}_$run.line 2> $O/order${OR}_$run.err || fail bench $O/order${OR}_$run.err
         python3 -c "
 import json; d=json.load(open('$O/order${OR}_$run.json'))['strong']
@@ -286,7 +286,7 @@ print('order $OR run $run T1', d['t1_ms'], {k: (v['eta'], max(v['shard_ms'])) fo
       cat $O/ab_steal.txt ;;
     r5_balance)   # projected eta(n): blocks dealt cyclically (0) vs by the next frame's cost (2), live-first order, three runs each
       for run in 1 2 3; do for BAL in 0 2; do
-        timeout -k 10 400 python bench.py --no-extra --no-cpu --no-explore --no-fast --steps 5 --strong-balance $BAL \
+        timeout -k 10 400 python bench.py --full --no-extra --no-cpu --no-explore --no-fast --steps 5 --strong-balance $BAL \
           --detail-out $O/bal${BAL}_$run.json > $O/bal${BAL}_$run.line 2> $O/bal${BAL}_$run.err || fail bench $O/bal${BAL}_$run.err
         python3 -c "
 import json; d=json.load(open('$O/bal${BAL}_$run.json'))['strong']

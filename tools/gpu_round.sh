@@ -31,15 +31,15 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail smoke $O/smoke.log
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py ${arg//,/ } --detail-out $O/bench_detail.json > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
+      timeout -k 10 600 python bench.py --full ${arg//,/ } --detail-out $O/bench_detail.json > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
       grep -E "\[(head|extra|strong|line)\]" $O/bench.err ;;
     gloo)   # bench.py starts its two ranks itself (no launcher), as `python bench.py --gpus N` would
-      timeout -k 10 600 python bench.py --gpus 2 --dist-backend gloo --steps 10 --detail-out $O/bench_gloo2_detail.json \
+      timeout -k 10 600 python bench.py --full --gpus 2 --dist-backend gloo --steps 10 --detail-out $O/bench_gloo2_detail.json \
         > $O/bench_gloo2.json 2> $O/bench_gloo2.err || fail "gloo rehearsal" $O/bench_gloo2.err
       grep -E "\[(head|strong|launch)\]" $O/bench_gloo2.err ;;
     gloorun)   # the same under torch.distributed.run (the driver's N>1 launch)
       timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-        bench.py --gpus 2 --dist-backend gloo --steps 10 --detail-out $O/bench_gloorun2_detail.json > $O/bench_gloorun2.json 2> $O/bench_gloorun2.err \
+        bench.py --full --gpus 2 --dist-backend gloo --steps 10 --detail-out $O/bench_gloorun2_detail.json > $O/bench_gloorun2.json 2> $O/bench_gloorun2.err \
         || fail "gloo rehearsal (torchrun)" $O/bench_gloorun2.err
       grep -E "\[(head|strong)\]" $O/bench_gloorun2.err ;;
     tune)

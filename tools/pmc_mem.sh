@@ -18,7 +18,7 @@ for set in "TA_TA_BUSY_sum TA_BUFFER_READ_WAVEFRONTS_sum GRBM_GUI_ACTIVE" \
            "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" \
            "TA_BUSY_max TA_BUSY_min TA_BUSY_avr"; do
   i=$((i+1))
-  timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $OUT/p$i -o run -- python3 bench.py --workload $W --no-extra --no-cpu --steps 5 "$@" > $OUT/log$i 2>&1 || { echo "pass $i ($set) failed"; grep -i "error\|invalid\|not found" $OUT/log$i | head -3; }
+  timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $OUT/p$i -o run -- python3 bench.py --full --workload $W --no-extra --no-cpu --steps 5 "$@" > $OUT/log$i 2>&1 || { echo "pass $i ($set) failed"; grep -i "error\|invalid\|not found" $OUT/log$i | head -3; }
 done
 python3 - <<'PY'
 import csv, glob, collections

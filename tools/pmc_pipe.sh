@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 W=${1:-hairball-diffuse-1920x1080}
 OUT=${2:-gpurun_out/pipe}
 SETS=${3:-"GRBM_GUI_ACTIVE TA_BUSY_avr TA_BUFFER_READ_WAVEFRONTS_sum;TD_BUSY_avr TCP_TOTAL_CACHE_ACCESSES_sum GRBM_COUNT"}
-B="--workload $W --no-extra --no-cpu --no-strong --bvh-cache /tmp/mrt_bvhcache"
+B="--full --workload $W --no-extra --no-cpu --no-strong --bvh-cache /tmp/mrt_bvhcache"
 mkdir -p $OUT
 timeout -k 10 60 rocprofv3 --list-avail > $OUT/avail.txt 2>&1 || { echo "list-avail failed"; exit 1; }
 timeout -k 10 300 python3 bench.py $B --steps 2 --warmup 1 > $OUT/bench_warm.log 2>&1 || { echo "warm run failed"; tail $OUT/bench_warm.log; exit 1; }
