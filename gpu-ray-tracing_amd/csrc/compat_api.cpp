@@ -1,0 +1,166 @@
+// compat_api.cpp — the implicit per-device tracers (mrt_bind_bvh / mrt_unbind_bvh /
+// mrt_trace) and the reference-compatible entry points of CudaTracerKernels.hh:42-52,
+// written against the public mrt_* functions of include/mrt.h only.
+#include <hip/hip_runtime.h>
+#include <climits>
+
+#include <cstdio>
+#include <cstdlib>
+#include <mutex>
+#include <string>
+
+#include "../../include/mrt.h"
+#include "trace_kernel.hpp"
+
+namespace {
+
+int fail(int code, const std::string& what) { return mrt::api_fail(code, what); }
+
+int hipFail(hipError_t e, const char* what) {
+    return fail(MRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// ---- implicit per-device tracers (convenience + reference-compat API) ----
+constexpr int kMaxDevices = 64;
+std::mutex g_devMu;
+mrt_tracer* g_devTracer[kMaxDevices] = {};
+
+mrt_tracer* device_tracer(int* err) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
+        *err = fail(MRT_ERR_NO_DEVICE, "no current HIP device");
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lock(g_devMu);
+    if (!g_devTracer[dev]) {
+        mrt_tracer* t = nullptr;
+        *err = mrt_tracer_create(dev, &t);
+        if (*err) return nullptr;
+        g_devTracer[dev] = t;
+    }
+    *err = MRT_OK;
+    return g_devTracer[dev];
+}
+
+// cutilSafeCall-style fatal error for the compat entry points
+// (reference cutil_inline_runtime.h:32-42).
+void compat_check(int rc, const char* file, int line) {
+    if (rc != MRT_OK) {
+        std::fprintf(stderr, "[%s,%d] (HIP error %d: %s)\n", file, line, rc, mrt_last_error_detail());
+        std::exit(-1);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrt_bind_bvh(const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
+                 const int32_t* triIndex, int64_t triIndexBytes) {
+    int err = 0;
+    mrt_tracer* t = device_tracer(&err);
+    if (!t) return err;
+    return mrt_tracer_bind(t, nodes, nodeBytes, woop, woopBytes, triIndex, triIndexBytes);
+}
+
+int mrt_unbind_bvh(void) {
+    int err = 0;
+    mrt_tracer* t = device_tracer(&err);
+    if (!t) return err;
+    return mrt_tracer_unbind(t);
+}
+
+int mrt_trace(const void* rays, void* results, int32_t numRays, int32_t anyHit, void* stream, float* outMs) {
+    int err = 0;
+    mrt_tracer* t = device_tracer(&err);
+    if (!t) return err;
+    const uint32_t flags = anyHit ? MRT_TRACE_ANY_HIT : 0u;
+    if (!outMs) return mrt_tracer_trace(t, rays, results, numRays, flags, nullptr, stream);
+    mrt_trace_info info;
+    const int rc = mrt_tracer_trace_timed(t, rays, results, numRays, flags, nullptr, stream, &info);
+    *outMs = info.kernel_ms;
+    return rc;
+}
+
+// ---- reference-compatible entry points --------------------------------------
+
+void bind_CudaBVHTexture(void* nodeBuf, int64_t nodeBufSize, void* triWoopBuf, int64_t triWoopSize,
+                         int32_t* triIndexBuf, int64_t triIndexSize) {
+    compat_check(mrt_bind_bvh(nodeBuf, nodeBufSize, triWoopBuf, triWoopSize, triIndexBuf, triIndexSize), __FILE__,
+                 __LINE__);
+}
+
+void unbind_CudaBVHTexture(void) { compat_check(mrt_unbind_bvh(), __FILE__, __LINE__); }
+
+float launch_tracingKernel(int32_t nthreads, int32_t* blockSize, int numRays, bool anyHit, void* rays,
+                           void* results, void* nodesA, void* nodesB, void* nodesC, void* nodesD, void* trisA,
+                           void* trisB, void* trisC, int32_t* triIndices) {
+    // The reference ignored nthreads/blockSize (CudaKernel::setGrid rewrote
+    // them) and read the BVH through the textures bound earlier; the node/tri
+    // pointers are accepted for ABI compatibility only.
+    (void)nthreads; (void)blockSize; (void)nodesA; (void)nodesB; (void)nodesC; (void)nodesD;
+    (void)trisA; (void)trisB; (void)trisC; (void)triIndices;
+    float ms = 0.0f;
+    compat_check(mrt_trace(rays, results, numRays, anyHit ? 1 : 0, nullptr, &ms), __FILE__, __LINE__);
+    return ms;
+}
+
+void copy_tracing_results(void* result_host, void* result_dev, int32_t size) {
+    const hipError_t e = hipMemcpy(result_host, result_dev, (size_t)size * 16u, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) compat_check(hipFail(e, "hipMemcpy"), __FILE__, __LINE__);
+}
+
+void launch_rayGenPrimaryKernel(int32_t nthreads, mrt_raygen_primary_input* in) {
+    (void)nthreads;
+    if (!in) compat_check(fail(MRT_ERR_INVALID_ARG, "null RayGenPrimaryInput"), __FILE__, __LINE__);
+    compat_check(mrt_raygen_primary(in->nscreenToWorld, in->origin, in->maxDist, in->w, in->h, in->indexToPixel,
+                                    in->rays, in->slotToID, in->idToSlot, nullptr),
+                 __FILE__, __LINE__);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) compat_check(hipFail(e, "hipDeviceSynchronize"), __FILE__, __LINE__);
+}
+
+void launch_rayGenAOKernel(int32_t nthreads, mrt_raygen_ao_input* in) {
+    (void)nthreads;
+    if (!in || in->firstInputSlot < 0)
+        compat_check(fail(MRT_ERR_INVALID_ARG, "bad RayGenAOInput"), __FILE__, __LINE__);
+    // inSlot = taskIdx + firstInputSlot; the hash and the output slots use taskIdx (RayGenKernels.cu:128-131,163)
+    const char* inRays = static_cast<const char*>(in->inRays);
+    const char* inResults = static_cast<const char*>(in->inResults);
+    compat_check(mrt_raygen_ao(inRays ? inRays + (int64_t)in->firstInputSlot * 32 : nullptr,
+                               inResults ? inResults + (int64_t)in->firstInputSlot * 16 : nullptr, in->numInputRays,
+                               static_cast<const float*>(in->normals), INT64_MAX, in->numSamples, in->maxDist,
+                               in->randomSeed, in->outRays, in->outIDToSlot, in->outSlotToID, nullptr),
+                 __FILE__, __LINE__);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) compat_check(hipFail(e, "hipDeviceSynchronize"), __FILE__, __LINE__);
+}
+
+void launch_reconstructKernel(int32_t nthreads, mrt_reconstruct_input* in) {
+    (void)nthreads;   // the reference's CudaKernel::setGrid(nthreads) shape; ours is fixed
+    if (!in) compat_check(fail(MRT_ERR_INVALID_ARG, "null ReconstructInput"), __FILE__, __LINE__);
+    const int32_t type = in->isAO ? MRT_RAY_AO : (in->isDiffuse ? MRT_RAY_DIFFUSE : MRT_RAY_PRIMARY);
+    compat_check(mrt_reconstruct(type, in->numRaysPerPrimary, in->firstPrimary, in->numPrimary, in->primarySlotToID,
+                                 in->primaryResults, in->batchIDToSlot, in->batchResults, in->triMaterialColor,
+                                 in->triShadedColor, in->pixels, nullptr),
+                 __FILE__, __LINE__);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) compat_check(hipFail(e, "hipDeviceSynchronize"), __FILE__, __LINE__);
+}
+
+int32_t launch_countHitsKernel(int32_t threads, const int32_t* blockSize, mrt_count_hits_input* in) {
+    (void)threads; (void)blockSize;   // launch shape of the reference (RendererKernels.cu:191-199)
+    if (!in) compat_check(fail(MRT_ERR_INVALID_ARG, "null CountHitsInput"), __FILE__, __LINE__);
+    int32_t* d = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(int32_t));
+    if (e != hipSuccess) compat_check(hipFail(e, "hipMalloc"), __FILE__, __LINE__);
+    compat_check(mrt_count_hits(in->rayResults, in->numRays, d, nullptr), __FILE__, __LINE__);
+    int32_t n = 0;
+    e = hipMemcpy(&n, d, sizeof(int32_t), hipMemcpyDeviceToHost);
+    const hipError_t f = hipFree(d);
+    if (e != hipSuccess) compat_check(hipFail(e, "hipMemcpy"), __FILE__, __LINE__);
+    if (f != hipSuccess) compat_check(hipFail(f, "hipFree"), __FILE__, __LINE__);
+    return n;
+}
+
+}  // extern "C"

@@ -112,8 +112,15 @@ typedef struct mrt_launch_cfg {
                                   (the first untimed) until it has eight timed samples, without blocking,
                                   after one untimed round; the median ranks them and a candidate
                                   replaces the fixed rule (stage 1) or the previous stage's winner only
-                                  when 3 % faster. A new batch size within 1/32 of a settled one of the
-                                  same variant and ray class (MRT_TRACE_SECONDARY batches are a class
+                                  when 3 % faster. Settling costs 32 untimed launches, then per stage of
+                                  n candidates (8, 10, 6) 4 * n * 3 - 1 launches (eight samples at three
+                                  per run of four: three cycles, the last run one launch short): 246
+                                  launches when no modifier clears the margin, 317 with stage 3, when each
+                                  timing is read by the next launch (mrt_tracer_trace_timed); asynchronous
+                                  launches add their in-flight lag at every stage end (256-328 measured).
+                                  The policy is csrc/tune.cpp, run on the CPU by tests/test_tune.py.
+                                  A new batch size within 1/32 of a settled one of the same variant
+                                  and ray class (MRT_TRACE_SECONDARY batches are a class
                                   of their own) takes the nearest settled schedule without exploring —
                                   a schedule tuned on another ray distribution of that class; such
                                   inherited entries are not exported by mrt_tracer_tune_export (an

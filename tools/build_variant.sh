@@ -17,7 +17,11 @@ fi
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fgpu-flush-denormals-to-zero -ffp-contract=off -Wall -Wno-unused-result -I$D/../include"
 /opt/rocm/bin/hipcc $HIPFLAGS -fno-slp-vectorize $FLAGS -c $D/csrc/trace_kernel.hip -o $B/trace_kernel.o
 /opt/rocm/bin/hipcc $HIPFLAGS $FLAGS -c $D/csrc/raygen_kernel.hip -o $B/raygen_kernel.o
-/opt/rocm/bin/hipcc $HIPFLAGS $FLAGS -x hip -c $D/csrc/mrt_api.cpp -o $B/mrt_api.o
-/opt/rocm/bin/hipcc $HIPFLAGS $FLAGS -x hip -c $D/csrc/wide_bvh.cpp -o $B/wide_bvh.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUT/libmrt.so $B/trace_kernel.o $B/raygen_kernel.o $B/mrt_api.o $B/wide_bvh.o
+OBJS="$B/trace_kernel.o $B/raygen_kernel.o"
+for src in $D/csrc/*.cpp; do   # mrt_api, tune, compat_api, wide_bvh (whichever the revision has)
+    obj=$B/$(basename $src .cpp).o
+    /opt/rocm/bin/hipcc $HIPFLAGS $FLAGS -x hip -c $src -o $obj
+    OBJS="$OBJS $obj"
+done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUT/libmrt.so $OBJS
 echo "built $OUT/libmrt.so ($FLAGS${REV:+ at $REV})"

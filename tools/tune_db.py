@@ -1,14 +1,14 @@
 """Builds gpu-ray-tracing_amd/mrt/tuned_schedules.json, the saved autotuner choices the
 bench locks at bind (the same schedule every run).
 
-The in-library autotuner ranks candidates from ~100 launches interleaved with each
-other, early in a process while clocks still ramp; here every candidate is timed in
-steady state instead: the GPU is warmed first, each candidate is locked in turn
+The in-library autotuner ranks candidates from 246-317 launches (csrc/tune.cpp; more with
+asynchronous launches in flight: 256-328 measured) interleaved with each other, early in
+a process while clocks still ramp; here every candidate is timed in steady state instead: the GPU is warmed first, each candidate is locked in turn
 (mrt_tracer_tune_import) and timed over interleaved rounds of back-to-back launches
 (HIP events): the eight ray-distribution schedules, each also with every stage-2
 modifier (spec_slack 4 / 6, the frontier tail toggled, 16 lane groups), then the two fastest against the
 fixed rule again; a challenger replaces the rule only when its median is 3 % faster
-(mrt_api.cpp kTuneMargin).
+(csrc/tune.cpp kTuneMargin).
 
   python tools/tune_db.py [--workload W ...] [--rounds 5] [--launches 20] [--out PATH]
 """
@@ -28,7 +28,7 @@ N_SCHEDULES, STAGE2 = 8, 5
 
 
 def variant_key(any_hit, exact, lds_stack=16, nodes=1, tail=False, secondary=False):
-    """mrt_api.cpp's tuning key of a speculative, stats-free launch: variant_key() | 512 for a
+    """The tuning key (mrt_api.cpp variant_key, csrc/tune.cpp) of a speculative, stats-free launch: variant_key() | 512 for a
     MRT_TRACE_SECONDARY batch."""
     return (int(any_hit) | 2 | (4 if exact else 0) | ({8: 0, 16: 1, 32: 2}[lds_stack] << 4) | (nodes << 6)
             | (256 if tail else 0) | (512 if secondary else 0))
@@ -101,7 +101,7 @@ def main():
                 for go in launches:
                     go()
                 torch.cuda.synchronize()
-            # the candidate equal to the fixed rule (mrt_api.cpp effective_cfg): the global queue for a
+            # the candidate equal to the fixed rule (csrc/tune.cpp effective_cfg): the global queue for a
             # BVH above the Infinity Cache, 12 waves/CU up to 3 rays per lane of a 16-wave grid, else 16
             g = e["gbvh"]
             cus = torch.cuda.get_device_properties(0).multi_processor_count
