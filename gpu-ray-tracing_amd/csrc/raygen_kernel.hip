@@ -16,6 +16,7 @@
 // contended atomics).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "../../include/mrt.h"
@@ -100,6 +101,9 @@ __global__ __launch_bounds__(kThreads) void ao_per_sample_kernel(AOArgs a) {
 // a rank's shard generated directly in its trace order, no gather of a frame
 // buffer. One thread per output ray: consecutive lanes write consecutive 32-B
 // rays; a block id and an input ray are shared by B and S consecutive lanes.
+// A frame of at most kMaxBatchSeeds batches carries its seeds in the kernel arguments; a
+// longer one reads them from seedTable (device memory, filled on the stream by
+// seed_fill_kernel launches that carry kMaxBatchSeeds seeds each in their arguments).
 constexpr int kMaxBatchSeeds = 256;
 struct AOBlocksArgs {
     const rg::RayRec* inRays;
@@ -116,8 +120,26 @@ struct AOBlocksArgs {
     const int32_t* blocks;
     rg::RayRec* out;
     uint32_t seeds[kMaxBatchSeeds];
+    const uint32_t* seedTable;   // kSeedTable kernels: one seed per batch of the frame (last: seeds[] stays where it was)
 };
 
+template <bool kSeedTable>
+__device__ inline uint32_t batch_seed(const AOBlocksArgs& a, int batch) {
+    return kSeedTable ? a.seedTable[batch] : a.seeds[batch];   // batch < the frame's batches: p < numInput
+}
+
+struct SeedFillArgs {
+    uint32_t* table;
+    int first, count;   // table[first + i] = seeds[i], i < count <= kMaxBatchSeeds
+    uint32_t seeds[kMaxBatchSeeds];
+};
+
+__global__ __launch_bounds__(kMaxBatchSeeds) void seed_fill_kernel(SeedFillArgs a) {
+    const int i = (int)threadIdx.x;
+    if (i < a.count) a.table[(int64_t)a.first + i] = a.seeds[i];
+}
+
+template <bool kSeedTable>
 __global__ __launch_bounds__(kThreads) void ao_blocks_kernel(AOBlocksArgs a) {
     const int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (j >= a.outRays) return;
@@ -129,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void ao_blocks_kernel(AOBlocksArgs a) {
     const int batch = p / a.batchInputs;
     const int2 res = a.inResults[2 * p];
     const rg::AOBasis b = rg::ao_basis(a.inRays[p], res.x, __int_as_float(res.y), a.normals, a.numTris,
-                                       a.seeds[batch], (uint32_t)(p - batch * a.batchInputs));
+                                       batch_seed<kSeedTable>(a, batch), (uint32_t)(p - batch * a.batchInputs));
     a.out[j] = rg::ao_sample(b, i, a.maxDist);
 }
 
@@ -142,6 +164,7 @@ __global__ __launch_bounds__(kThreads) void ao_blocks_kernel(AOBlocksArgs a) {
 // arithmetic, same bits. Four rays per thread: a 2 M-ray shard is 2 025 workgroups, one
 // round of the device, so the dependent load chain is paid once, not four times.
 constexpr int kTileRays = 1024;
+template <bool kSeedTable>
 __global__ __launch_bounds__(kThreads) void ao_blocks_tiled_kernel(AOBlocksArgs a) {
     __shared__ rg::AOBasis basis[kThreads];
     __shared__ rg::V3 sample[kThreads];
@@ -157,8 +180,8 @@ __global__ __launch_bounds__(kThreads) void ao_blocks_tiled_kernel(AOBlocksArgs 
         const int p = p0 + t;
         const int batch = p / a.batchInputs;
         const int2 res = a.inResults[2 * p];
-        basis[t] = rg::ao_basis(a.inRays[p], res.x, __int_as_float(res.y), a.normals, a.numTris, a.seeds[batch],
-                                (uint32_t)(p - batch * a.batchInputs));
+        basis[t] = rg::ao_basis(a.inRays[p], res.x, __int_as_float(res.y), a.normals, a.numTris,
+                                batch_seed<kSeedTable>(a, batch), (uint32_t)(p - batch * a.batchInputs));
     }
     if (kThreads - 1 - t < S) sample[kThreads - 1 - t] = rg::ao_sample_xyz(kThreads - 1 - t);
     __syncthreads();
@@ -171,7 +194,8 @@ __global__ __launch_bounds__(kThreads) void ao_blocks_tiled_kernel(AOBlocksArgs 
 }
 
 // mrt_shard_blocks: a rank's blocks of the frame's secondary-ray order (block i to rank
-// i % world) and their trace order. Two launches, no host sync:
+// i % world) and their trace order. A list of at most kOrderMax blocks: two launches, no host
+// sync (longer lists: the tile kernels below):
 //   block_live_kernel   one wave per listed block: its live rays = the samples of its input
 //                       rays whose primary hit (RayGenKernels.cu:117-227: a missed primary's
 //                       samples get tmax = -1), as the sort key B - live (the frame's partial
@@ -194,8 +218,9 @@ __device__ inline int shard_block_id(const ShardArgs& a, int j) { return a.rank 
 
 __global__ __launch_bounds__(kThreads) void block_live_kernel(ShardArgs a) {
     const int lane = (int)(threadIdx.x & 63);
-    const int j = (int)((blockIdx.x * kThreads + threadIdx.x) >> 6);
-    if (j >= a.numBlocks) return;
+    const int64_t jj = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);   // one wave per entry
+    if (jj >= a.numBlocks) return;
+    const int j = (int)jj;
     const int64_t g0 = (int64_t)shard_block_id(a, j) * a.blockRays;
     const int64_t g1 = min(g0 + a.blockRays, a.totalRays);
     const int64_t p0 = g0 / a.numSamples, p1 = (g1 - 1) / a.numSamples;   // input rays touching the block
@@ -228,18 +253,29 @@ __device__ inline int wave_scan_incl(int v) {
     return v;
 }
 
-__global__ __launch_bounds__(kOrderThreads) void block_order_kernel(ShardArgs a) {
-    constexpr int kWaves = kOrderThreads / 64;
-    __shared__ uint16_t key[kOrderMax];
-    __shared__ uint16_t idx[2][kOrderMax];
-    __shared__ int waveTot[kWaves][16];
-    __shared__ int wavePre[kWaves][16];
+constexpr int kOrderWaves = kOrderThreads / 64;
+#if defined(__HIP_DEVICE_COMPILE__)
+constexpr int kOrderLdsBytes = 3 * kOrderMax * (int)sizeof(uint16_t) + 2 * kOrderWaves * 16 * (int)sizeof(int);
+constexpr int kTileLdsBytes = kOrderLdsBytes + (kKeyMax + 1) * (int)sizeof(int);   // + block_tile_sort_kernel's histogram
+#if defined(__gfx950__)
+constexpr int kDeviceLdsBytes = 160 * 1024;
+#else
+constexpr int kDeviceLdsBytes = 64 * 1024;
+#endif
+static_assert(kTileLdsBytes <= kDeviceLdsBytes,
+              "mrt_shard_blocks' LDS sort (block_order_kernel, block_tile_sort_kernel) holds 16384 list entries in "
+              "about 98-114 KB of static LDS: it needs gfx950's 160 KB per workgroup, and this device target has "
+              "64 KB - build with ARCH=gfx950");
+#endif
+
+// The stable sort of n <= kOrderMax list entries in LDS, by all of one workgroup's threads:
+// key[i] and idx[0][i] = i are set (not yet synchronised); on return idx[src][0..n) is the
+// order (src returned; the caller synchronises before it reads another thread's entries).
+__device__ __forceinline__ int order_tile_in_lds(uint16_t* key, uint16_t (*idx)[kOrderMax],
+                                                 int (*waveTot)[16], int (*wavePre)[16], int n) {
+    constexpr int kWaves = kOrderWaves;
     static_assert((16 * kWaves) % 64 == 0, "the prefix wave walks (digit, wave) entries 64 at a time");
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, n = a.numBlocks;
-    for (int i = t; i < n; i += kOrderThreads) {
-        key[i] = (uint16_t)a.out[i];
-        idx[0][i] = (uint16_t)i;
-    }
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     const int chunk = (n + kOrderThreads - 1) / kOrderThreads;
     const int lo = min(n, t * chunk), hi = min(n, lo + chunk);
     int src = 0;
@@ -291,13 +327,130 @@ __global__ __launch_bounds__(kOrderThreads) void block_order_kernel(ShardArgs a)
             idx[src ^ 1][pos] = v;
         }
     }
+    return src;
+}
+
+__global__ __launch_bounds__(kOrderThreads) void block_order_kernel(ShardArgs a) {
+    __shared__ uint16_t key[kOrderMax];
+    __shared__ uint16_t idx[2][kOrderMax];
+    __shared__ int waveTot[kOrderWaves][16];
+    __shared__ int wavePre[kOrderWaves][16];
+    const int t = (int)threadIdx.x, n = a.numBlocks;
+    for (int i = t; i < n; i += kOrderThreads) {
+        key[i] = (uint16_t)a.out[i];
+        idx[0][i] = (uint16_t)i;
+    }
+    const int src = order_tile_in_lds(key, idx, waveTot, wavePre, n);
     __syncthreads();
     for (int i = t; i < n; i += kOrderThreads) a.out[i] = shard_block_id(a, idx[src][i]);
 }
 
+// Lists longer than kOrderMax (mrt_shard_blocks): three launches after block_live_kernel, each
+// a phase that reads what every workgroup of the one before wrote — the stream orders them;
+// no workgroup ever waits for another.
+//   block_tile_sort_kernel     workgroup = one tile of <= kOrderMax consecutive list entries:
+//                              the LDS sort above; the tile-sorted (key, index in tile) pairs to
+//                              pairs[], the tile's counts per key — read off the run boundaries
+//                              of the sorted keys — to table[key][tile];
+//   block_hist_scan_kernel     one workgroup: table -> its exclusive prefix sum in memory order,
+//                              key-major, tile-minor = where each tile's run of each key starts
+//                              in the sorted list (equal keys: lower tile first, so list order);
+//   block_tile_scatter_kernel  workgroup = tile: entry i of the tile's order, of key k, goes to
+//                              table[k][tile] + (i - the run's first i), as its block id.
+// The keys stay in the list until block_tile_sort_kernel has read them; only the scatter
+// writes block ids there.
+struct TileArgs {
+    ShardArgs s;
+    uint32_t* pairs;   // [s.numBlocks]: key << 16 | index in tile, tile-sorted
+    int32_t* table;    // [kKeyMax + 1][numTiles]
+    int numTiles;
+};
+
+__global__ __launch_bounds__(kOrderThreads) void block_tile_sort_kernel(TileArgs a) {
+    __shared__ uint16_t key[kOrderMax];
+    __shared__ uint16_t idx[2][kOrderMax];
+    __shared__ int waveTot[kOrderWaves][16];
+    __shared__ int wavePre[kOrderWaves][16];
+    __shared__ int count[kKeyMax + 1];
+    const int t = (int)threadIdx.x, tile = (int)blockIdx.x;
+    const int64_t base = (int64_t)tile * kOrderMax;
+    const int n = (int)min((int64_t)kOrderMax, (int64_t)a.s.numBlocks - base);   // the last tile is short
+    if (tile >= a.numTiles || n <= 0) return;                                   // workgroup-uniform
+    for (int i = t; i < n; i += kOrderThreads) {
+        key[i] = (uint16_t)(a.s.out[base + i] & kKeyMax);
+        idx[0][i] = (uint16_t)i;
+    }
+    for (int k = t; k <= kKeyMax; k += kOrderThreads) count[k] = 0;
+    const int src = order_tile_in_lds(key, idx, waveTot, wavePre, n);
+    __syncthreads();
+    const uint16_t* ord = idx[src];
+    for (int i = t; i < n; i += kOrderThreads) {   // a run's last entry: its end
+        const int v = ord[i], k = key[v];
+        a.pairs[base + i] = (uint32_t)k << 16 | (uint32_t)v;
+        if (i + 1 == n || key[ord[i + 1]] != k) count[k] = i + 1;
+    }
+    __syncthreads();
+    for (int i = t; i < n; i += kOrderThreads) {   // a run's first entry: end - start
+        const int k = key[ord[i]];
+        if (i == 0 || key[ord[i - 1]] != k) count[k] -= i;
+    }
+    __syncthreads();
+    for (int k = t; k <= kKeyMax; k += kOrderThreads) a.table[(int64_t)k * a.numTiles + tile] = count[k];
+}
+
+// In place; numTiles rounds of 4 * kOrderThreads = kKeyMax + 1 consecutive entries (so no
+// ragged end), one int4 per thread, the next round's load issued before this round's barriers.
+__global__ __launch_bounds__(kOrderThreads) void block_hist_scan_kernel(int32_t* table, int numTiles) {
+    static_assert(4 * kOrderThreads == kKeyMax + 1, "a round is one int4 per thread");
+    __shared__ int waveTot[kOrderWaves];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    int4* tv = reinterpret_cast<int4*>(table);
+    int carry = 0;
+    int4 next = numTiles > 0 ? tv[t] : make_int4(0, 0, 0, 0);
+    for (int r = 0; r < numTiles; r++) {
+        const int4 v = next;
+        if (r + 1 < numTiles) next = tv[(int64_t)(r + 1) * kOrderThreads + t];
+        const int sum = v.x + v.y + v.z + v.w;
+        const int incl = wave_scan_incl(sum);
+        if (lane == 63) waveTot[wave] = incl;
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < kOrderWaves; w++) {
+            const int x = waveTot[w];
+            all += x;
+            before += w < wave ? x : 0;
+        }
+        const int ex = carry + before + incl - sum;
+        tv[(int64_t)r * kOrderThreads + t] = make_int4(ex, ex + v.x, ex + v.x + v.y, ex + v.x + v.y + v.z);
+        carry += all;
+        __syncthreads();   // waveTot is rewritten next round
+    }
+}
+
+__global__ __launch_bounds__(kOrderThreads) void block_tile_scatter_kernel(TileArgs a) {
+    __shared__ int first[kKeyMax + 1];   // per key of the tile: its run's place in the list - its first i
+    const int t = (int)threadIdx.x, tile = (int)blockIdx.x;
+    const int64_t base = (int64_t)tile * kOrderMax;
+    const int n = (int)min((int64_t)kOrderMax, (int64_t)a.s.numBlocks - base);
+    if (tile >= a.numTiles || n <= 0) return;
+    for (int i = t; i < n; i += kOrderThreads) {
+        const int k = (int)(a.pairs[base + i] >> 16) & kKeyMax;
+        if (i == 0 || ((int)(a.pairs[base + i - 1] >> 16) & kKeyMax) != k)
+            first[k] = a.table[(int64_t)k * a.numTiles + tile] - i;
+    }
+    __syncthreads();
+    for (int i = t; i < n; i += kOrderThreads) {
+        const uint32_t p = a.pairs[base + i];
+        const int64_t pos = (int64_t)first[(int)(p >> 16) & kKeyMax] + i;   // every run's first entry set first[]
+        const int64_t j = base + (int)(p & 0xFFFF);
+        if (pos >= 0 && pos < a.s.numBlocks && j < a.s.numBlocks) a.s.out[pos] = shard_block_id(a.s, (int)j);
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void block_list_kernel(ShardArgs a) {
-    const int j = (int)(blockIdx.x * kThreads + threadIdx.x);
-    if (j < a.numBlocks) a.out[j] = shard_block_id(a, j);
+    const int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (j < a.numBlocks) a.out[j] = shard_block_id(a, (int)j);
 }
 
 // Per block: hits among its rays (id >= 0, RendererKernels.cu:131), one partial.
@@ -430,6 +583,26 @@ int hip_fail(hipError_t e, const char* what) {
     return api_fail(MRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// Whether [p, p + bytes) lies in memory the device can address, as far as the runtime can tell
+// without touching the stream: p is registered with it (device, managed or pinned host memory)
+// and, where it reports the allocation's range, the range holds the bytes. False for any other
+// pointer, and when there is no device.
+bool device_memory_holds(const void* p, size_t bytes) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();   // a query's failure is an answer, not a launch error
+        return false;
+    }
+    if (at.type == hipMemoryTypeUnregistered) return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;               // registered, but of a kind the runtime gives no range for
+    }
+    return static_cast<const char*>(p) + bytes <= static_cast<const char*>(base) + size;
+}
+
 constexpr int kCountBlocks = 1024;
 
 }  // namespace
@@ -511,7 +684,6 @@ int mrt_raygen_ao_blocks(const void* inRays, const void* inResults, int32_t numI
     if (total > INT32_MAX) return api_fail(MRT_ERR_TOO_LARGE, "too many frame rays");
     const int64_t needBatches = ((int64_t)numInputRays + batchInputRays - 1) / batchInputRays;
     if (numBatches < needBatches) return api_fail(MRT_ERR_INVALID_ARG, "fewer batch seeds than batches");
-    if (needBatches > kMaxBatchSeeds) return api_fail(MRT_ERR_TOO_LARGE, "more than 256 batches in the frame");
     const int64_t nb = (total + blockRays - 1) / blockRays;
     if (numBlocks > nb) return api_fail(MRT_ERR_INVALID_ARG, "more blocks listed than the frame has");
     if (numOutRays > (int64_t)numBlocks * blockRays || numOutRays < (int64_t)(numBlocks > 0 ? numBlocks - 1 : 0) * blockRays)
@@ -533,16 +705,42 @@ int mrt_raygen_ao_blocks(const void* inRays, const void* inResults, int32_t numI
     a.outRays = numOutRays;
     a.blocks = blocks;
     a.out = static_cast<rg::RayRec*>(outRays);
-    for (int64_t k = 0; k < needBatches; k++) a.seeds[k] = batchSeeds[k];
-    if (blockRays % kTileRays == 0 && kTileRays % numSamples == 0 && kTileRays / numSamples <= kThreads &&
-        numSamples <= kThreads)   // the tile's input rays and its sample points each fit one LDS slot per thread
-        hipLaunchKernelGGL(ao_blocks_tiled_kernel, dim3((unsigned)((numOutRays + kTileRays - 1) / kTileRays)),
-                           dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-    else
-        hipLaunchKernelGGL(ao_blocks_kernel, dim3((unsigned)((numOutRays + kThreads - 1) / kThreads)), dim3(kThreads),
-                           0, static_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MRT_OK : hip_fail(e, "raygen ao blocks launch");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool tiled = blockRays % kTileRays == 0 && kTileRays % numSamples == 0 &&
+                       kTileRays / numSamples <= kThreads && numSamples <= kThreads;
+    // tiled: the tile's input rays and its sample points each fit one LDS slot per thread
+    const dim3 grid((unsigned)(tiled ? (numOutRays + kTileRays - 1) / kTileRays : (numOutRays + kThreads - 1) / kThreads));
+    if (needBatches <= kMaxBatchSeeds) {
+        for (int64_t k = 0; k < needBatches; k++) a.seeds[k] = batchSeeds[k];
+        if (tiled) hipLaunchKernelGGL(ao_blocks_tiled_kernel<false>, grid, dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL(ao_blocks_kernel<false>, grid, dim3(kThreads), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? MRT_OK : hip_fail(e, "raygen ao blocks launch");
+    }
+    // More batches than the arguments hold: the seeds go to stream-ordered scratch through fill
+    // launches whose arguments carry them (copied at launch, so the caller's array is free on
+    // return; no copy from pageable memory, no host sync), the generator reads them there.
+    uint32_t* table = nullptr;
+    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&table), (size_t)needBatches * sizeof(uint32_t), s);
+    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(batch seeds)");
+    SeedFillArgs f{};
+    f.table = table;
+    for (int64_t first = 0; first < needBatches && e == hipSuccess; first += kMaxBatchSeeds) {
+        f.first = (int)first;
+        f.count = (int)std::min<int64_t>(kMaxBatchSeeds, needBatches - first);
+        for (int k = 0; k < f.count; k++) f.seeds[k] = batchSeeds[first + k];
+        hipLaunchKernelGGL(seed_fill_kernel, dim3(1), dim3(kMaxBatchSeeds), 0, s, f);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        a.seedTable = table;
+        if (tiled) hipLaunchKernelGGL(ao_blocks_tiled_kernel<true>, grid, dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL(ao_blocks_kernel<true>, grid, dim3(kThreads), 0, s, a);
+        e = hipGetLastError();
+    }
+    const hipError_t fr = hipFreeAsync(table, s);
+    if (e != hipSuccess) return hip_fail(e, "raygen ao blocks launch");
+    return fr == hipSuccess ? MRT_OK : hip_fail(fr, "hipFreeAsync(batch seeds)");
 }
 
 int mrt_shard_blocks(const void* primaryResults, int32_t numPrimary, int32_t numSamples, int32_t blockRays,
@@ -560,8 +758,6 @@ int mrt_shard_blocks(const void* primaryResults, int32_t numPrimary, int32_t num
     *numRays = mine * blockRays - (lastMine ? nb * blockRays - total : 0);
     if (mine == 0 || !blocks) return MRT_OK;   // blocks NULL: a size query
     if (capacity < mine) return api_fail(MRT_ERR_TOO_LARGE, "block list capacity below the shard's blocks");
-    if (order == 1 && mine > kOrderMax)
-        return api_fail(MRT_ERR_TOO_LARGE, "live-first order holds at most 16384 blocks per rank (use larger blocks)");
     if (order == 1 && !primaryResults) return api_fail(MRT_ERR_INVALID_ARG, "null primary results");
     hipStream_t s = static_cast<hipStream_t>(stream);
     ShardArgs a{};
@@ -579,10 +775,40 @@ int mrt_shard_blocks(const void* primaryResults, int32_t numPrimary, int32_t num
         const hipError_t e = hipGetLastError();
         return e == hipSuccess ? MRT_OK : hip_fail(e, "shard block list launch");
     }
-    hipLaunchKernelGGL(block_live_kernel, dim3((unsigned)((mine * 64 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
-    hipLaunchKernelGGL(block_order_kernel, dim3(1), dim3(kOrderThreads), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MRT_OK : hip_fail(e, "shard order launch");
+    const dim3 liveGrid((unsigned)((mine * 64 + kThreads - 1) / kThreads));
+    if (mine <= kOrderMax) {   // the list fits one workgroup's LDS: two launches, no scratch
+        hipLaunchKernelGGL(block_live_kernel, liveGrid, dim3(kThreads), 0, s, a);
+        hipLaunchKernelGGL(block_order_kernel, dim3(1), dim3(kOrderThreads), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? MRT_OK : hip_fail(e, "shard order launch");
+    }
+    // A long list is written by many workgroups over four launches: before anything is taken or
+    // launched, the list the caller gave must really be there — capacity is the caller's word, the
+    // allocation's extent the runtime's — and so must the results it is ordered by.
+    if (!device_memory_holds(blocks, (size_t)mine * sizeof(int32_t)))
+        return api_fail(MRT_ERR_TOO_LARGE, "no device memory of the shard's blocks behind the block list (" +
+                                               std::to_string(mine) + " entries)");
+    if (!device_memory_holds(primaryResults, (size_t)numPrimary * 4 * sizeof(int32_t)))
+        return api_fail(MRT_ERR_INVALID_ARG, "no device memory of numPrimary results behind primaryResults");
+    // Tiles of kOrderMax entries: stream-ordered scratch for the key-by-tile table (first: its
+    // int4 accesses stay aligned) and the tile-sorted pairs, four launches, no host sync.
+    TileArgs ta{};
+    ta.s = a;
+    ta.numTiles = (int)((mine + kOrderMax - 1) / kOrderMax);
+    const size_t tableInts = (size_t)(kKeyMax + 1) * ta.numTiles;
+    void* scratch = nullptr;
+    hipError_t e = hipMallocAsync(&scratch, (tableInts + (size_t)mine) * sizeof(int32_t), s);
+    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(shard order scratch)");
+    ta.table = static_cast<int32_t*>(scratch);
+    ta.pairs = reinterpret_cast<uint32_t*>(ta.table + tableInts);
+    hipLaunchKernelGGL(block_live_kernel, liveGrid, dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(block_tile_sort_kernel, dim3(ta.numTiles), dim3(kOrderThreads), 0, s, ta);
+    hipLaunchKernelGGL(block_hist_scan_kernel, dim3(1), dim3(kOrderThreads), 0, s, ta.table, ta.numTiles);
+    hipLaunchKernelGGL(block_tile_scatter_kernel, dim3(ta.numTiles), dim3(kOrderThreads), 0, s, ta);
+    e = hipGetLastError();
+    const hipError_t f = hipFreeAsync(scratch, s);
+    if (e != hipSuccess) return hip_fail(e, "shard order launch");
+    return f == hipSuccess ? MRT_OK : hip_fail(f, "hipFreeAsync(shard order scratch)");
 }
 
 int mrt_count_hits(const void* results, int32_t numRays, int32_t* hitCount, void* stream) {

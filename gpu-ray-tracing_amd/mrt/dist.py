@@ -110,9 +110,14 @@ def shard_blocks_device(n: int, world: int, rank: int, block: int, owners=None, 
     number of rays they hold). priority: a device tensor (e.g. live_block_weights); the
     order is shard_blocks' (a stable sort of the same keys), so gather_results /
     shard_spans with the same priority on the host put the results back."""
+    if block <= 0:
+        raise ValueError("shard_blocks_device: block must be positive")
     nblocks = -(-n // block)
     if owners is not None:
-        mine_h = np.flatnonzero(np.asarray(owners) == rank)
+        owners = np.asarray(owners)
+        if len(owners) != nblocks:
+            raise ValueError(f"shard_blocks_device: {len(owners)} block owners for {nblocks} blocks of {block} rays")
+        mine_h = np.flatnonzero(owners == rank)
     else:
         mine_h = np.arange(rank, nblocks, world)
     partial = n % block

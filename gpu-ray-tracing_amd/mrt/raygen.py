@@ -85,7 +85,8 @@ class DeviceRayGen:
         hold at positions blocks[i] * block_rays + [0, block_rays), concatenated in list order —
         e.g. one rank's shard of the frame in its trace order, generated directly. blocks: int32
         device tensor; num_rays: the rays listed (a partial last block of the frame, when listed,
-        must be the last entry: mrt.dist.shard_blocks_device keeps it there)."""
+        must be the last entry: mrt.dist.shard_blocks_device keeps it there). Any number of
+        batches: above 256 the seeds are read from stream-ordered device scratch."""
         if self.normals is None:
             raise _lib.MrtError("DeviceRayGen.ao_blocks needs the scene's triangle normals (pass scene=)")
         if blocks.dtype != torch.int32 or blocks.dim() != 1 or blocks.device != torch.device(self.device):
@@ -104,7 +105,10 @@ class DeviceRayGen:
         """mrt_shard_blocks: rank's blocks (block i to rank i % world) of the frame's AO/diffuse
         ray order, in frame order (order 0) or live blocks first (1: decreasing live rays from
         the primary pass's results, ties in frame order, a partial last block last), as an int32
-        device tensor, and the rays they hold — two small launches, no host sync."""
+        device tensor, and the rays they hold. Any number of blocks per rank (the frame holds at
+        most 2^31 - 1 rays): up to 16 384 are ordered by two small launches; a longer list in
+        16 384-entry tiles, four launches and 5 bytes per block + 16 KB per tile of scratch taken and
+        returned on the stream. No host sync either way."""
         n = C.c_int32(0)
         m = C.c_int64(0)
         _lib.check(self.lib.mrt_shard_blocks(None, primary.size, num_samples, block_rays, world, rank, 0, None, 0,

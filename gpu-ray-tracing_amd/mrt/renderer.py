@@ -146,7 +146,9 @@ class Renderer:
         (the order next_batch's batches hold them in), generated directly in list order on the
         device (mrt_raygen_ao_blocks) — a rank's shard of the frame, or the whole frame with
         its costly blocks first, with no frame-order buffer and no gather. Bit-identical to
-        the same positions of the batches. num_rays: the rays listed (mrt.dist.shard_blocks_device)."""
+        the same positions of the batches. num_rays: the rays listed (mrt.dist.shard_blocks_device).
+        A frame of any number of batches (any max_batch next_batch accepts): above 256 the
+        generator reads the batch seeds from device scratch instead of its arguments."""
         if self.ray_type == RAY_PRIMARY or self.primary is None:
             raise _lib.MrtError("secondary_blocks needs an AO or diffuse frame (set_params, begin_frame)")
         return self.gen.ao_blocks(self.primary, self.num_samples, self._max_dist(), self.batch_seeds(),
@@ -158,7 +160,9 @@ class Renderer:
         trace order on the device: block i of block_rays rays to rank i % world, live blocks
         first (order 1) or in frame order (0) — mrt_shard_blocks, then secondary_blocks. Two
         ranks' shards hold disjoint rays; together, the frame (mrt.dist.gather_results with
-        block=block_rays and priority=mrt.dist.live_priority(...) puts results back)."""
+        block=block_rays and priority=mrt.dist.live_priority(...) puts results back). Any
+        block_rays >= 1 and any number of batches: the limit is the frame's, 2^31 - 1 rays (a
+        shard of more than 16 384 blocks is ordered in tiles, with stream-ordered scratch)."""
         if self.ray_type == RAY_PRIMARY or self.primary is None:
             raise _lib.MrtError("shard needs an AO or diffuse frame (set_params, begin_frame)")
         blocks, n = self.gen.shard_blocks(self.primary, self.num_samples, block_rays, world, rank, order, stream)

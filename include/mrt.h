@@ -298,7 +298,12 @@ int  mrt_raygen_ao(const void* inRays, const void* inResults, int32_t numInputRa
  * batches hold there (mrt_raygen_ao of batch k). blocks: device int32[numBlocks], any
  * order (e.g. a rank's shard, its costly blocks first). Only the frame's last block can
  * be partial; when listed it must be the last entry, and numOutRays = the listed rays
- * ((numBlocks-1)*blockRays + its length; else numBlocks*blockRays). At most 256 batches.
+ * ((numBlocks-1)*blockRays + its length; else numBlocks*blockRays). Any number of batches
+ * (the frame holds at most INT32_MAX rays): up to 256 batches travel in the kernel's arguments;
+ * above that the seeds are written to scratch taken and returned on the stream
+ * (hipMallocAsync / hipFreeAsync; a failed allocation is MRT_ERR_HIP) by one small fill launch
+ * per 256 batches. Either way batchSeeds may be freed when the call returns, and the call is
+ * stream-ordered without a host sync.
  * A block id outside [0, blocks in the frame) is not checked on the host (the list is device
  * memory): its output rays are left unwritten. */
 int  mrt_raygen_ao_blocks(const void* inRays, const void* inResults, int32_t numInputRays, const float* triNormals,
@@ -313,9 +318,17 @@ int  mrt_raygen_ao_blocks(const void* inRays, const void* inResults, int32_t num
  * number of live rays (samples whose primary ray hit, read from primaryResults — the primary
  * pass's RayResult[numPrimary]; a missed primary's samples are degenerate, tmax = -1), ties in
  * frame order, the frame's partial last block last (live counts quantized to 12 bits when
- * blockRays > 4094; order 1 holds at most 16384 blocks per rank). blocks: device
- * int32[capacity] (NULL: only *numBlocks / *numRays are set); *numBlocks and *numRays (host) =
- * the rank's blocks and the rays they hold, known without the device. Stream-ordered, no host sync. */
+ * blockRays > 4094). Any number of blocks per rank that blocks[] holds (the frame: at most
+ * INT32_MAX rays): a list of at most 16384 blocks is sorted by one workgroup in LDS, two launches
+ * and no scratch; a longer one in 16384-entry tiles, four launches and 5 bytes per listed block + 16
+ * KB per tile of scratch taken and returned on the stream (hipMallocAsync / hipFreeAsync; a
+ * failed allocation is MRT_ERR_HIP). Before a tiled sort takes or launches anything the runtime is
+ * asked (two pointer queries on the host, no sync) whether device-addressable memory of the rank's
+ * blocks lies behind blocks (else MRT_ERR_TOO_LARGE, like a capacity that is too small) and of
+ * numPrimary results behind primaryResults (else MRT_ERR_INVALID_ARG). blocks: device int32[capacity] (NULL: only *numBlocks /
+ * *numRays are set; capacity below the rank's blocks: MRT_ERR_TOO_LARGE, nothing written);
+ * *numBlocks and *numRays (host) = the rank's blocks and the rays they hold, known without the
+ * device. Stream-ordered, no host sync. */
 int  mrt_shard_blocks(const void* primaryResults, int32_t numPrimary, int32_t numSamples, int32_t blockRays,
                       int32_t world, int32_t rank, int32_t order, int32_t* blocks, int32_t capacity,
                       int32_t* numBlocks, int64_t* numRays, void* stream);
