@@ -65,6 +65,16 @@ void create_compact2(const BvhNode& root, const Scene& scene, Compact2& out);
 // [v0-v2, v1-v2, cross(v0-v2, v1-v2), v2].
 void woopify(const Vec3f& v0, const Vec3f& v1, const Vec3f& v2, Vec4f out[3]);
 
+// Refit in place for moved vertices of a fixed topology (refit.cpp; no reference
+// counterpart): every leaf's Woop rows from its triangles' new vertices
+// (triIndex -> triangles -> vertices), every leaf box the min/max of its triangles'
+// vertices, every inner box the union of its child's two boxes, bottom-up. Words
+// 12-15 of the nodes, triIndex and the terminators stay; an empty leaf keeps its
+// stored box and adds nothing to its ancestors. False (nothing written) for a
+// triIndex entry or vertex index out of range, or buffers that are not a tree.
+bool refit_compact2(Compact2& c, const float* vertices, int64_t numVertices, const int32_t* triangles,
+                    int64_t numTriangles, std::string* err);
+
 // bvhcache .dat: S32 layout, then per buffer S64 byte count + bytes, little
 // endian (CudaBVH.cc:79-97,113-116; Buffer.cc:327-360). Layout 5 = Compact2.
 bool save_dat(const std::string& path, const Compact2& c, std::string* err);

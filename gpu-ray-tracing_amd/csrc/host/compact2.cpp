@@ -16,15 +16,9 @@
 namespace mrt {
 
 void woopify(const Vec3f& v0, const Vec3f& v1, const Vec3f& v2, Vec4f out[3]) {   // CudaBVH.cc:361-380
-    Mat4f mtx;
-    mtx.set_col(0, Vec4f(v0 - v2, 0.0f));
-    mtx.set_col(1, Vec4f(v1 - v2, 0.0f));
-    mtx.set_col(2, Vec4f(cross(v0 - v2, v1 - v2), 0.0f));
-    mtx.set_col(3, Vec4f(v2, 1.0f));
-    mtx = inverted(mtx);
-    out[0] = Vec4f(mtx(2, 0), mtx(2, 1), mtx(2, 2), -mtx(2, 3));
-    out[1] = mtx.row(0);
-    out[2] = mtx.row(1);
+    float rows[12];
+    woop::woop_rows(&v0.x, &v1.x, &v2.x, rows);
+    for (int r = 0; r < 3; r++) out[r] = Vec4f(rows[4 * r], rows[4 * r + 1], rows[4 * r + 2], rows[4 * r + 3]);
 }
 
 namespace {
@@ -82,11 +76,10 @@ void create_compact2(const BvhNode& rootIn, const Scene& scene, Compact2& out) {
             cidx[i] = ~(int32_t)(out.woop.size() / 4);
             for (const int32_t tri : child->tris) {
                 const Vec3i& t = scene.triangles[tri];
-                Vec4f w[3];
-                woopify(scene.vertices[t.x], scene.vertices[t.y], scene.vertices[t.z], w);
-                if (w[0].x == 0.0f) w[0].x = 0.0f;   // -0.0 would read as a terminator
-                for (int r = 0; r < 3; r++)
-                    for (int c = 0; c < 4; c++) out.woop.push_back((int32_t)float_bits(w[r][c]));
+                float w[12];
+                woop::woop_rows(&scene.vertices[t.x].x, &scene.vertices[t.y].x, &scene.vertices[t.z].x, w);
+                woop::woop_guard(w);   // -0.0 would read as a terminator
+                for (int k = 0; k < 12; k++) out.woop.push_back((int32_t)float_bits(w[k]));
                 out.triIndex.push_back(tri);
                 out.triIndex.push_back(0);
                 out.triIndex.push_back(0);

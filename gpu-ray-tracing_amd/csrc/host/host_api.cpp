@@ -264,6 +264,15 @@ int mrth_bvh_get_stats(const mrth_bvh* b, mrth_bvh_stats* out) {
     return MRTH_OK;
 }
 
+int mrth_bvh_refit(mrth_bvh* b, const float* vertices, int64_t numVertices, const int32_t* triangles,
+                   int64_t numTriangles) {
+    if (!b) return fail(MRTH_ERR_INVALID_ARG, "null bvh");
+    std::string err;
+    if (!mrt::refit_compact2(b->c2, vertices, numVertices, triangles, numTriangles, &err))
+        return fail(MRTH_ERR_INVALID_ARG, err);
+    return MRTH_OK;
+}
+
 void mrth_woopify(const float v0[3], const float v1[3], const float v2[3], float out[12]) {
     mrt::Vec4f w[3];
     mrt::woopify(v3(v0), v3(v1), v3(v2), w);

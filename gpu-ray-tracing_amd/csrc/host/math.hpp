@@ -10,11 +10,15 @@
 #include <cstdint>
 #include <cstring>
 
+#include "../woop_common.hpp"
+
 namespace mrt {
 
-inline float fw_min(float a, float b) { return (a < b) ? a : b; }
-inline float fw_max(float a, float b) { return (a > b) ? a : b; }
-inline float fw_rcp(float a) { return (a != 0.0f) ? 1.0f / a : 0.0f; }   // Math.hh:113
+// FW::min / FW::max / rcp, the 3x3 determinant and the cofactor inverse below are
+// woop_common.hpp's: the refit kernels restate the Woop transform with them.
+using woop::fw_min;
+using woop::fw_max;
+using woop::fw_rcp;   // Math.hh:113
 inline uint32_t float_bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 inline float bits_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
@@ -123,33 +127,12 @@ inline Vec4f operator*(const Mat4f& a, const Vec4f& v) {   // Math.hh:996-1007
     return r;
 }
 
-// 3x3 determinant in the reference's term order (Math.hh:935-940).
-inline float det3(const float v[3][3]) {
-    return v[0][0] * v[1][1] * v[2][2] - v[0][0] * v[1][2] * v[2][1] + v[1][0] * v[2][1] * v[0][2] -
-           v[1][0] * v[2][2] * v[0][1] + v[2][0] * v[0][1] * v[1][2] - v[2][0] * v[0][2] * v[1][1];
-}
+using woop::det3;   // Math.hh:935-940
 
-// Cofactor inverse with the reference's quirk: d accumulates L * det, and the
-// result is r * rcp(d) * L (Math.hh:962-984).
+// Cofactor inverse with the reference's quirk (Math.hh:962-984; woop_common.hpp).
 inline Mat4f inverted(const Mat4f& a) {
     Mat4f r;
-    float d = 0.0f;
-    float si = 1.0f;
-    for (int i = 0; i < 4; i++) {
-        float sj = si;
-        for (int j = 0; j < 4; j++) {
-            float sub[3][3];
-            for (int k = 0; k < 3; k++)
-                for (int l = 0; l < 3; l++) sub[k][l] = a((k < j) ? k : k + 1, (l < i) ? l : l + 1);
-            const float dd = det3(sub) * sj;
-            r(i, j) = dd;
-            d += dd * a(j, i);
-            sj = -sj;
-        }
-        si = -si;
-    }
-    const float rd = fw_rcp(d);
-    for (int i = 0; i < 16; i++) r.m[i] = (r.m[i] * rd) * 4.0f;
+    woop::inverted4(a.m, r.m);
     return r;
 }
 

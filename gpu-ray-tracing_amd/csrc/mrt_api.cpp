@@ -16,6 +16,8 @@
 #include <vector>
 
 #include "../../include/mrt.h"
+#include "refit_kernel.hpp"
+#include "refit_plan.hpp"
 #include "trace_kernel.hpp"
 #include "tune.hpp"
 
@@ -60,6 +62,24 @@ struct mrt_tracer {
     int wideStackCap = mrt::kStackCapacity;
     int wideStackBound = mrt::kStackCapacity - 1;   // wide_stack_bound of the derived tree (the tail's headroom)
     double bindMs = 0.0;                   // wall time of the last bind / wide derivation (mrt_trace_info)
+    // Exact form only: per wide child the Compact2 slot (binary node * 2 + side) its box was
+    // copied from, -1 = absent — from the collapse that produced wideNodes (a refit copies the
+    // refitted boxes along it; collapsing refitted nodes again would choose other children).
+    std::vector<int32_t> wideSrc;
+
+    // The refit plan (mrt_tracer_refit), built on the first refit after a bind or set_config
+    // and dropped by bind, unbind and set_config: the nodes by height level, the wide source
+    // map and the refit's scratch, on the device.
+    bool planBuilt = false;
+    int32_t* planOrder = nullptr;      // numNodes node indices, level by level
+    int32_t* planOffsets = nullptr;    // levels + 1 offsets into planOrder
+    int32_t* planWideSrc = nullptr;    // wideSrc on the device (null: no exact wide array)
+    uint8_t* planValid = nullptr;      // 2 per node, rewritten by every refit
+    unsigned long long* planSkipped = nullptr;   // out-of-range references skipped since the last refit_info
+    std::vector<int64_t> planLevels;   // the level offsets on the host
+    int64_t planBytes = 0;
+    int refitLaunches = 0;             // kernel launches of the last refit
+    bool refitLaunched = false;        // a refit may still be running
 
     // Launch scratch, one set per stream the handle has launched on: the stack
     // spill slab, the queue heads and the overflow counter are written by a
@@ -327,6 +347,22 @@ int workspace_for(mrt_tracer* t, void* stream, int totalLanes, int ldsStack, int
     return MRT_OK;
 }
 
+// Forgets the refit plan (bind, unbind, set_config, destroy; the handle's mutex held).
+void drop_plan(mrt_tracer* t) {
+    if (t->refitLaunched) (void)hipDeviceSynchronize();   // a refit may still read the plan
+    t->refitLaunched = false;
+    for (void* p : {(void*)t->planOrder, (void*)t->planOffsets, (void*)t->planWideSrc, (void*)t->planValid,
+                    (void*)t->planSkipped})
+        if (p) (void)hipFree(p);
+    t->planOrder = t->planOffsets = t->planWideSrc = nullptr;
+    t->planValid = nullptr;
+    t->planSkipped = nullptr;
+    t->planLevels.clear();
+    t->planBytes = 0;
+    t->planBuilt = false;
+    t->refitLaunches = 0;
+}
+
 // Largest wide-traversal stack a tracer sizes its spill slab for (entries per lane).
 constexpr int kMaxWideStack = 1024;
 
@@ -339,6 +375,8 @@ int refresh_wide(mrt_tracer* t) {
     DeviceGuard guard(t->device);
     // launches in flight may still read the old array: wait for this handle's own
     if (int rc = wait_all_workspaces(t)) return rc;
+    if (t->refitLaunched) MRT_HIP(hipDeviceSynchronize());   // a refit's gather may still write it
+    t->refitLaunched = false;
     if (t->wideNodes) MRT_HIP(hipFree(t->wideNodes));
     t->wideNodes = nullptr;
     t->wideBytes = 0;
@@ -346,6 +384,7 @@ int refresh_wide(mrt_tracer* t) {
     t->wideFormat = mrt::kNodeCompact2;
     t->wideStackCap = mrt::kStackCapacity;
     t->wideStackBound = mrt::kStackCapacity - 1;
+    t->wideSrc.clear();
     if (want) {
         std::vector<int32_t> host((size_t)(t->nodeBytes / 4));
         MRT_HIP(hipMemcpy(host.data(), t->nodes, (size_t)t->nodeBytes, hipMemcpyDeviceToHost));
@@ -362,7 +401,7 @@ int refresh_wide(mrt_tracer* t) {
         int format = mrt::kNodeWide4;
         // The quantized form when asked for and every box quantizes; else the exact one.
         if (want == 2 && mrt::build_wide4q(host.data(), t->nodeBytes / 64, &wide, wx, slots)) format = mrt::kNodeWide4Q;
-        else wide = mrt::build_wide4(host.data(), t->nodeBytes / 64, wx, slots);
+        else wide = mrt::build_wide4(host.data(), t->nodeBytes / 64, wx, slots, &t->wideSrc);
         t->wideLeafCounts = counts;
         const int nodeWords = format == mrt::kNodeWide4 ? 32 : 16;
         const int64_t need = mrt::wide_stack_bound(wide.data(), (int64_t)wide.size() / nodeWords, nodeWords);
@@ -570,6 +609,100 @@ int trace_impl(mrt_tracer* t, const void* rays, void* results, int32_t numRays, 
     return fill_info(t, v, a, ws, info);
 }
 
+// ---- refit (mrt_tracer_refit): the plan and the launches ---------------------------
+
+// Builds the refit plan of the bound tree (the handle's mutex held). Synchronous: the
+// Compact2 nodes come to the host once for their child refs (topology only: a refit in
+// flight changes boxes, never words 12-15).
+int build_plan(mrt_tracer* t) {
+    if (t->planBuilt) return MRT_OK;
+    const int64_t numNodes = t->nodeBytes / 64;
+    std::vector<int32_t> host((size_t)(t->nodeBytes / 4));
+    MRT_HIP(hipMemcpy(host.data(), t->nodes, (size_t)t->nodeBytes, hipMemcpyDeviceToHost));
+    mrt::RefitLevels lv;
+    if (const char* why = mrt::refit_levels(host.data(), numNodes, &lv))
+        return fail(MRT_ERR_INVALID_ARG, std::string("refit: the bound nodes are not a tree: ") + why);
+    std::vector<int32_t> offsets(lv.offsets.begin(), lv.offsets.end());   // < 2^26 nodes
+    drop_plan(t);
+    MRT_HIP(hipMalloc(&t->planOrder, lv.order.size() * 4));
+    MRT_HIP(hipMemcpy(t->planOrder, lv.order.data(), lv.order.size() * 4, hipMemcpyHostToDevice));
+    MRT_HIP(hipMalloc(&t->planOffsets, offsets.size() * 4));
+    MRT_HIP(hipMemcpy(t->planOffsets, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice));
+    MRT_HIP(hipMalloc(&t->planValid, (size_t)numNodes * 2));
+    MRT_HIP(hipMalloc(&t->planSkipped, sizeof(unsigned long long)));
+    MRT_HIP(hipMemset(t->planSkipped, 0, sizeof(unsigned long long)));
+    t->planBytes = (int64_t)lv.order.size() * 4 + (int64_t)offsets.size() * 4 + numNodes * 2 + 8;
+    if (t->wideNodes && t->wideFormat == mrt::kNodeWide4 && (int64_t)t->wideSrc.size() == t->wideBytes / 128 * 4) {
+        MRT_HIP(hipMalloc(&t->planWideSrc, t->wideSrc.size() * 4));
+        MRT_HIP(hipMemcpy(t->planWideSrc, t->wideSrc.data(), t->wideSrc.size() * 4, hipMemcpyHostToDevice));
+        t->planBytes += (int64_t)t->wideSrc.size() * 4;
+    }
+    t->planLevels = lv.offsets;
+    t->planBuilt = true;
+    return MRT_OK;
+}
+
+int refit_impl(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,
+               int64_t numTriangles, void* stream) {
+    if (!t) return fail(MRT_ERR_INVALID_ARG, "null tracer");
+    if (numVertices < 0 || numTriangles < 0 || (numVertices && !vertices) || (numTriangles && !triangles))
+        return fail(MRT_ERR_INVALID_ARG, "refit: bad vertex / triangle arrays");
+    std::lock_guard<std::mutex> lock(t->mu);
+    if (!t->bound) return fail(MRT_ERR_NOT_BOUND, "refit before bind (no BVH)");
+    DeviceGuard guard(t->device);
+    if (int rc = build_plan(t)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+
+    mrt::RefitArgs a{};
+    a.nodes = static_cast<uint32_t*>(const_cast<void*>(t->nodes));   // refit writes the bound buffers (mrt.h)
+    a.numNodes = (int)(t->nodeBytes / 64);
+    a.woop = static_cast<uint32_t*>(const_cast<void*>(t->woop));
+    a.woopSlots = (int)(t->woopBytes / 16);
+    a.triIndex = t->triIndex;
+    a.vertices = vertices;
+    a.numVertices = numVertices;
+    a.triangles = triangles;
+    a.numTriangles = numTriangles;
+    a.valid = t->planValid;
+    a.skipped = t->planSkipped;
+
+    int launches = 0;
+    t->refitLaunched = true;
+    MRT_HIP(mrt::launch_refit_leaves(a, s));
+    launches++;
+    const int levels = (int)t->planLevels.size() - 1;
+    for (int l = 1; l < levels; l++) {
+        const int begin = (int)t->planLevels[(size_t)l], count = (int)(t->planLevels[(size_t)l + 1] - begin);
+        if (count > mrt::kRefitTailNodes) {
+            MRT_HIP(mrt::launch_refit_level(a, t->planOrder, begin, count, s));
+            launches++;
+            continue;
+        }
+        // level sizes never grow with the height: this one and all above it fit one workgroup
+        MRT_HIP(mrt::launch_refit_tail(a, t->planOrder, t->planOffsets, l, levels, s));
+        launches++;
+        break;
+    }
+    if (t->planWideSrc && t->wideNodes && t->wideFormat == mrt::kNodeWide4) {
+        MRT_HIP(mrt::launch_refit_wide(a, t->planWideSrc, static_cast<uint32_t*>(t->wideNodes), (int)(t->wideBytes / 128), s));
+        launches++;
+    }
+    t->refitLaunches = launches;
+    if (t->wideNodes && t->wideFormat == mrt::kNodeWide4Q) {
+        // The quantized form has no in-place update: derive it again from the refitted
+        // nodes through the bind-time host path (synchronous and slow; mrt.h).
+        MRT_HIP(hipStreamSynchronize(s));
+        t->wideBuiltFor = -1;
+        if (int rc = refresh_wide(t)) return rc;
+        // the exact form as a fallback would need a new source map on the device
+        if (t->wideFormat == mrt::kNodeWide4) {
+            t->planBuilt = false;
+            return build_plan(t);
+        }
+    }
+    return MRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -635,6 +768,7 @@ int mrt_tracer_destroy(mrt_tracer* t) {
     if (!t) return MRT_OK;
     {
         DeviceGuard guard(t->device);
+        drop_plan(t);
         if (t->wideNodes) (void)hipFree(t->wideNodes);
         (void)wait_all_workspaces(t);   // event waits: the streams may already be destroyed
         for (mrt::Workspace* w : t->workspaces) {
@@ -672,6 +806,7 @@ int mrt_tracer_bind(mrt_tracer* t, const void* nodes, int64_t nodeBytes, const v
     t->wideBuiltFor = -1;   // a new BVH: its wide nodes are derived now (if configured)
     DeviceGuard guard(t->device);
     tune_reset(t);          // and its schedules are tuned again
+    drop_plan(t);
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = refresh_wide(t);
     t->bindMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -684,6 +819,8 @@ int mrt_tracer_unbind(mrt_tracer* t) {
     t->bound = false;
     t->nodes = t->woop = nullptr;
     t->triIndex = nullptr;
+    DeviceGuard guard(t->device);
+    drop_plan(t);
     return refresh_wide(t);
 }
 
@@ -709,6 +846,7 @@ int mrt_tracer_set_config(mrt_tracer* t, const mrt_launch_cfg* cfg) {
     t->cfg = c;
     DeviceGuard guard(t->device);
     tune_reset(t);
+    drop_plan(t);
     const auto t0 = std::chrono::steady_clock::now();
     const int built = t->wideBuiltFor;
     const int rc = refresh_wide(t);
@@ -773,6 +911,68 @@ int mrt_tracer_stack_overflows(mrt_tracer* t, int64_t* count, int32_t reset) {
         if (reset) MRT_HIP(hipMemset(w->status, 0, sizeof(int)));
     }
     *count = total;
+    return MRT_OK;
+}
+
+int mrt_tracer_refit(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,
+                     int64_t numTriangles, void* stream) {
+    return refit_impl(t, vertices, numVertices, triangles, numTriangles, stream);
+}
+
+int mrt_tracer_refit_info(mrt_tracer* t, mrt_refit_info* info) {
+    if (!t || !info) return fail(MRT_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(t->mu);
+    std::memset(info, 0, sizeof(*info));
+    if (!t->planBuilt) return MRT_OK;
+    DeviceGuard guard(t->device);
+    if (t->refitLaunched) MRT_HIP(hipDeviceSynchronize());
+    t->refitLaunched = false;
+    unsigned long long skipped = 0;
+    MRT_HIP(hipMemcpy(&skipped, t->planSkipped, sizeof(skipped), hipMemcpyDeviceToHost));
+    MRT_HIP(hipMemset(t->planSkipped, 0, sizeof(skipped)));
+    info->levels = (int32_t)t->planLevels.size() - 1;
+    info->launches = t->refitLaunches;
+    info->plan_bytes = t->planBytes;
+    info->skipped_refs = (int64_t)skipped;
+    return MRT_OK;
+}
+
+int mrt_tracer_copy_wide_nodes(mrt_tracer* t, void* out, int64_t capacity, int64_t* bytes) {
+    if (!t || !bytes) return fail(MRT_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(t->mu);
+    *bytes = t->wideNodes ? t->wideBytes : 0;
+    if (!out || *bytes == 0) return MRT_OK;
+    if (capacity < *bytes) return fail(MRT_ERR_TOO_LARGE, "copy_wide_nodes: output buffer too small");
+    DeviceGuard guard(t->device);
+    MRT_HIP(hipDeviceSynchronize());   // refits in flight on any stream write the array
+    t->refitLaunched = false;
+    MRT_HIP(hipMemcpy(out, t->wideNodes, (size_t)*bytes, hipMemcpyDeviceToHost));
+    return MRT_OK;
+}
+
+int mrt_refit_plan(const void* nodes, int64_t nodeBytes, int32_t* order, int64_t* levelOffsets, int32_t levelCapacity,
+                   int32_t* numLevels, int32_t* wideSrc, int64_t wideSrcCapacity, int64_t* numWideSrc) {
+    if (!nodes || nodeBytes <= 0 || nodeBytes % 64 != 0 || !numLevels || levelCapacity < 0 || wideSrcCapacity < 0)
+        return fail(MRT_ERR_INVALID_ARG, "refit_plan: bad arguments");
+    const auto* n = static_cast<const int32_t*>(nodes);
+    mrt::RefitLevels lv;
+    if (const char* why = mrt::refit_levels(n, nodeBytes / 64, &lv))
+        return fail(MRT_ERR_INVALID_ARG, std::string("refit_plan: ") + why);
+    *numLevels = lv.levels();
+    if (order) std::memcpy(order, lv.order.data(), lv.order.size() * 4);
+    if (levelOffsets) {
+        if (levelCapacity < (int32_t)lv.offsets.size()) return fail(MRT_ERR_TOO_LARGE, "refit_plan: levelOffsets too small");
+        std::memcpy(levelOffsets, lv.offsets.data(), lv.offsets.size() * 8);
+    }
+    if (numWideSrc) {
+        std::vector<int32_t> src;
+        (void)mrt::build_wide4(n, nodeBytes / 64, nullptr, 0, &src);
+        *numWideSrc = (int64_t)src.size();
+        if (wideSrc) {
+            if (wideSrcCapacity < *numWideSrc) return fail(MRT_ERR_TOO_LARGE, "refit_plan: wideSrc too small");
+            std::memcpy(wideSrc, src.data(), src.size() * 4);
+        }
+    }
     return MRT_OK;
 }
 

@@ -87,8 +87,11 @@ struct TraceVariant {
 // leaf_counts_fit(woopSlots) (woop indices below 2^27).
 constexpr int kWideLeafAddrBits = 27;
 bool leaf_counts_fit(int64_t woopSlots);
+// srcMap (optional): four entries per wide node, the Compact2 slot (binary node * 2 +
+// side) whose box wide child c copies, -1 for an absent child: what a refit needs to
+// refresh the array's planes without collapsing again (refit_plan.hpp).
 std::vector<uint32_t> build_wide4(const int32_t* nodes, int64_t numNodes, const int32_t* woopX = nullptr,
-                                  int64_t woopSlots = 0);
+                                  int64_t woopSlots = 0, std::vector<int32_t>* srcMap = nullptr);
 // The most stack entries (sentinel excluded) a traversal of a 4-wide node array
 // can hold: the maximum over nodes of the pushes of all their ancestors plus
 // their own (each node pushes all but one of its children when every child is

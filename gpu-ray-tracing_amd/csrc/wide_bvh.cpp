@@ -57,6 +57,7 @@ namespace {
 struct Child {
     int32_t ref;
     float lo[3], hi[3];
+    int32_t src;   // the Compact2 slot the box was read from: binary node * 2 + side
 };
 
 float as_float(int32_t i) {
@@ -67,8 +68,10 @@ float as_float(int32_t i) {
 
 void binary_children(const int32_t* nodes, int32_t ref, Child out[2]) {
     const int32_t* n = nodes + (int64_t)(ref / 4) * 16;
-    out[0] = Child{n[12], {as_float(n[0]), as_float(n[2]), as_float(n[8])}, {as_float(n[1]), as_float(n[3]), as_float(n[9])}};
-    out[1] = Child{n[13], {as_float(n[4]), as_float(n[6]), as_float(n[10])}, {as_float(n[5]), as_float(n[7]), as_float(n[11])}};
+    const int32_t src = (ref / 4) * 2;
+    out[0] = Child{n[12], {as_float(n[0]), as_float(n[2]), as_float(n[8])}, {as_float(n[1]), as_float(n[3]), as_float(n[9])}, src};
+    out[1] = Child{n[13], {as_float(n[4]), as_float(n[6]), as_float(n[10])}, {as_float(n[5]), as_float(n[7]), as_float(n[11])},
+                   src + 1};
 }
 
 double half_area(const Child& c) {
@@ -311,14 +314,17 @@ bool build_wide4q(const int32_t* nodes, int64_t numNodes, std::vector<uint32_t>*
     return ok;
 }
 
-std::vector<uint32_t> build_wide4(const int32_t* nodes, int64_t numNodes, const int32_t* woopX, int64_t woopSlots) {
+std::vector<uint32_t> build_wide4(const int32_t* nodes, int64_t numNodes, const int32_t* woopX, int64_t woopSlots,
+                                  std::vector<int32_t>* srcMap) {
     std::vector<uint32_t> out;
+    if (srcMap) srcMap->clear();
     if (numNodes <= 0) return out;
     // Pass 1: number the wide nodes depth first (binary node -> wide index).
     std::vector<int32_t> wideOf, order;
     number_wide(nodes, numNodes, wideOf, order);
     // Pass 2: write the nodes.
     out.assign(order.size() * 32, 0u);
+    if (srcMap) srcMap->assign(order.size() * 4, -1);
     parallel_for((int64_t)((order.size() + 4095) / 4096), [&](int64_t chunk) {
     Child ch[4];
     const size_t end = std::min(order.size(), (size_t)(chunk + 1) * 4096);
@@ -343,6 +349,7 @@ std::vector<uint32_t> build_wide4(const int32_t* nodes, int64_t numNodes, const 
                 std::memcpy(&o[(2 * k + f4) * 4 + pair + 1], &hi[k], 4);
             }
             o[6 * 4 + c] = (uint32_t)ref;
+            if (srcMap && c < n) (*srcMap)[w * 4 + c] = ch[c].src;
         }
     }
     });

@@ -27,6 +27,7 @@ MRT_TRACE_LOCKSTEP_OFF = 1 << 2
 MRT_TRACE_STATS = 1 << 3
 MRT_TRACE_SECONDARY = 1 << 4
 MRT_ERR_INVALID_ARG = 1
+MRT_ERR_NOT_BOUND = 2
 MRT_ERR_STACK_OVERFLOW = 6
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
@@ -48,6 +49,10 @@ class TraceInfo(C.Structure):
 class BindInfo(C.Structure):
     _fields_ = [("bind_ms", C.c_double), ("wide_bytes", i64), ("wide_format", i32), ("stack_capacity", i32),
                 ("stack_bound", i32)]
+
+
+class RefitInfo(C.Structure):
+    _fields_ = [("levels", i32), ("launches", i32), ("plan_bytes", i64), ("skipped_refs", i64)]
 
 
 class TunedSchedule(C.Structure):
@@ -86,6 +91,10 @@ TRACE_SYMBOLS = [
     ("mrt_tracer_trace", i32, [vp, vp, vp, i32, u32, vp, vp]),
     ("mrt_tracer_trace_timed", i32, [vp, vp, vp, i32, u32, vp, vp, C.POINTER(TraceInfo)]),
     ("mrt_tracer_stack_overflows", i32, [vp, C.POINTER(i64), i32]),
+    ("mrt_tracer_refit", i32, [vp, vp, i64, vp, i64, vp]),
+    ("mrt_tracer_refit_info", i32, [vp, C.POINTER(RefitInfo)]),
+    ("mrt_tracer_copy_wide_nodes", i32, [vp, vp, i64, C.POINTER(i64)]),
+    ("mrt_refit_plan", i32, [vp, i64, vp, vp, i32, C.POINTER(i32), vp, i64, C.POINTER(i64)]),
     ("mrt_derive_wide_nodes", i32, [vp, i64, vp, i64, i32, vp, i64, C.POINTER(i64)]),
     ("mrt_bind_bvh", i32, [vp, i64, vp, i64, vp, i64]),
     ("mrt_unbind_bvh", i32, []),
@@ -136,6 +145,7 @@ HOST_SYMBOLS = [
     ("mrth_bvh_buffers", i32, [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64),
                                C.POINTER(vp), C.POINTER(i64)]),
     ("mrth_bvh_get_stats", i32, [vp, C.POINTER(BvhStats)]),
+    ("mrth_bvh_refit", i32, [vp, vp, i64, vp, i64]),
     ("mrth_woopify", None, [C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
     ("mrth_pixel_table", i32, [i32, i32, vp]),
     ("mrth_primary_rays", i32, [C.POINTER(HostCamera), i32, i32, vp, vp]),

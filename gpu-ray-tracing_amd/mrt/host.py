@@ -216,6 +216,14 @@ class Bvh:
 
         return grab(pn, nb.value), grab(pw, wb.value), grab(pt, tb.value)
 
+    def refit(self, vertices, triangles) -> None:
+        """Refit in place for moved vertices of the triangles the BVH was built over
+        (mrth_bvh_refit): new Woop rows, leaf boxes from whole triangles, inner boxes
+        bottom-up; the topology, triIndex and the terminators stay."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        _lib.check_host(_lib.host_lib().mrth_bvh_refit(self._h, _ptr(v), len(v), _ptr(t), len(t)))
+
     def stats(self) -> dict:
         s = _lib.BvhStats()
         _lib.check_host(_lib.host_lib().mrth_bvh_get_stats(self._h, C.byref(s)))

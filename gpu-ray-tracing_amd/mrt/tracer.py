@@ -104,6 +104,26 @@ class RayBuffer:
         return self.results_numpy()[:, 1].view(np.float32)
 
 
+def refit_plan(nodes, wide: bool = True):
+    """Host-only (mrt_refit_plan): (order int32[n], level offsets int64[levels + 1], wide
+    source map int32[4 * wide nodes] or None) of a Compact2 node array."""
+    lib = _lib.trace_lib()
+    n = np.ascontiguousarray(nodes).view(np.int32)
+    order = np.empty(n.size // 16, np.int32)
+    levels = C.c_int32()
+    _lib.check(lib.mrt_refit_plan(n.ctypes.data, n.nbytes, None, None, 0, C.byref(levels), None, 0, None))
+    offsets = np.empty(levels.value + 1, np.int64)
+    nsrc = C.c_int64()
+    _lib.check(lib.mrt_refit_plan(n.ctypes.data, n.nbytes, order.ctypes.data, offsets.ctypes.data, len(offsets),
+                                  C.byref(levels), None, 0, C.byref(nsrc) if wide else None))
+    src = None
+    if wide:
+        src = np.empty(nsrc.value, np.int32)
+        _lib.check(lib.mrt_refit_plan(n.ctypes.data, n.nbytes, None, None, 0, C.byref(levels), src.ctypes.data,
+                                      src.size, C.byref(nsrc)))
+    return order, offsets, src
+
+
 class Tracer:
     """Persistent-wave BVH tracer for one HIP device (mirror of CudaTracer)."""
 
@@ -161,6 +181,43 @@ class Tracer:
         _lib.check(self.lib.mrt_tracer_bind(self._h, bvh.nodes.data_ptr(), bvh.node_bytes, bvh.woop.data_ptr(),
                                             bvh.woop_bytes, bvh.tri_index.data_ptr(), bvh.tri_index_bytes))
         self.bvh = bvh
+
+    # -- refit (moving geometry, fixed topology) ---------------------------------
+    def refit(self, vertices, triangles, stream=None) -> None:
+        """Refit the bound BVH in place for moved vertices (mrt_tracer_refit): stream-ordered,
+        no host sync after the first call. vertices float32 [nv, 3], triangles int32 [nt, 3]
+        (the triangles the BVH was built over) as device tensors; numpy arrays are uploaded.
+        Writes the bound GpuBvh's nodes and woop tensors."""
+        if self.bvh is None:
+            raise _lib.MrtError("Tracer: No BVH!")
+        dev = self.bvh.device
+
+        def on_device(a, dtype, np_dtype):
+            if isinstance(a, torch.Tensor):
+                return a.to(dev, dtype).contiguous().view(-1, 3)
+            a = np.ascontiguousarray(a, np_dtype).reshape(-1, 3)
+            return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        v = on_device(vertices, torch.float32, np.float32)
+        t = on_device(triangles, torch.int32, np.int32)
+        _lib.check(self.lib.mrt_tracer_refit(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0],
+                                             _stream_ptr(stream)))
+        self._refit_inputs = (v, t)   # the launches may still read them
+
+    def refit_info(self) -> dict:
+        """Blocking: levels, launches of the last refit, plan bytes, and the out-of-range
+        references skipped since the last call (mrt_tracer_refit_info)."""
+        r = _lib.RefitInfo()
+        _lib.check(self.lib.mrt_tracer_refit_info(self._h, C.byref(r)))
+        return {k: getattr(r, k) for k, _ in r._fields_}
+
+    def wide_nodes(self) -> np.ndarray:
+        """Blocking copy of the derived 4-wide node array as uint32 (empty with wide = 0)."""
+        n = C.c_int64()
+        _lib.check(self.lib.mrt_tracer_copy_wide_nodes(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value // 4, np.uint32)
+        if n.value:
+            _lib.check(self.lib.mrt_tracer_copy_wide_nodes(self._h, out.ctypes.data, out.nbytes, C.byref(n)))
+        return out
 
     def flags(self, rays: RayBuffer, exact_rcp=False, speculative=True, stats=False) -> int:
         f = 0 if rays.need_closest_hit else _lib.MRT_TRACE_ANY_HIT

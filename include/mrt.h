@@ -202,13 +202,27 @@ typedef struct mrt_tuned_schedule {
 } mrt_tuned_schedule;
 enum { MRT_TUNE_VERSION = 11 };   /* 11: round 6 (schedules re-tuned on the round-6 library) */
 
+/* What mrt_tracer_refit_info reports. */
+typedef struct mrt_refit_info {
+    int32_t levels;            /* height levels of the bound tree (level 0: nodes with two leaf children)  */
+    int32_t launches;          /* kernel launches of the last refit: 1 for the leaves, 1 per level >= 1 of
+                                  more than 1024 nodes, 1 for all smaller levels together, 1 for the exact
+                                  4-wide array (cfg.wide 1)                                              */
+    int64_t plan_bytes;        /* device bytes of the refit plan: 4 per node (the level order), 2 per node
+                                  (scratch), 4 per level, and 16 per wide node (cfg.wide 1)              */
+    int64_t skipped_refs;      /* leaf triangles the refits since the last call left out because their
+                                  triIndex entry or one of their vertex indices was out of range        */
+} mrt_refit_info;
+
 /* ---- handle API -------------------------------------------------------- */
 int  mrt_tracer_create(int device, mrt_tracer** out);
 int  mrt_tracer_destroy(mrt_tracer* t);
 
 /* Bind a Compact2 BVH (device pointers, borrowed). Replaces bind_CudaBVHTexture
  * (CudaTracerKernels.hh:44); unlike the reference it may be called again to
- * re-bind a new BVH (the reference never re-bound, CudaTracer.cc:142-146). */
+ * re-bind a new BVH (the reference never re-bound, CudaTracer.cc:142-146).
+ * Tracing only reads the buffers; mrt_tracer_refit WRITES nodes and woop in place,
+ * so a caller that refits must bind writable memory. */
 int  mrt_tracer_bind(mrt_tracer* t,
                      const void* nodes, int64_t nodeBytes,
                      const void* woop, int64_t woopBytes,
@@ -244,6 +258,66 @@ int  mrt_tracer_trace_timed(mrt_tracer* t, const void* rays, void* results, int3
 /* Stack overflows of asynchronous launches since the last reset, summed over the
  * handle's streams (synchronises them). reset != 0 zeroes the counters. */
 int  mrt_tracer_stack_overflows(mrt_tracer* t, int64_t* count, int32_t reset);
+
+/* Refit the bound BVH on the device for moved vertices of a FIXED topology (animated or
+ * deforming meshes; no reference counterpart). vertices (3 floats each) and triangles (3
+ * vertex indices each; the triangles the BVH was built over, triIndex refers to them) are
+ * DEVICE pointers. The call rewrites, in the bound nodes and woop buffers (which must be
+ * writable) and in the library's derived 4-wide array, exactly what depends on vertex
+ * positions: every leaf is walked from its first Woop slot in steps of three up to its
+ * terminator, its Woop rows recomputed (bit-identical to mrth_bvh_refit / a host build of
+ * the same vertices), its box set to the min/max of its triangles' vertices; inner boxes are
+ * unions of their child's two boxes, one launch per height level, bottom-up. Words 12-15 of
+ * the nodes, triIndex and the terminators are untouched; an empty leaf keeps its box.
+ *   - Limits: a leaf box covers the whole triangle also where the SBVH builder had clipped
+ *     the reference to a spatial split, so refitted boxes are correct but may be looser than
+ *     built ones (traces get slower, never wrong); the tree is not re-optimised, so large
+ *     deformations degrade it — rebuild (mrth_bvh_build + bind) when that shows.
+ *   - A triIndex entry outside [0, numTriangles) or a vertex index outside [0, numVertices)
+ *     is never dereferenced: that triangle keeps its old rows, is left out of its leaf's
+ *     box, and is counted (mrt_refit_info.skipped_refs). Nothing is reported here.
+ *   - Ordering: stream-ordered on `stream` (a hipStream_t, NULL = the null stream) without a
+ *     host sync, after the first refit following a bind or set_config, which builds the
+ *     refit plan (one synchronous copy of the nodes to the host; mrt_refit_info.plan_bytes
+ *     on the device until the next bind, unbind or set_config). The refit runs after this
+ *     handle's traces enqueued on `stream` before it, and traces enqueued on `stream` after
+ *     it see the refitted tree. A trace on ANOTHER stream that overlaps a refit reads a
+ *     half-updated tree: ordering those (events, synchronisation) is the caller's job.
+ *   - Kept: the autotuner's schedules, the workspaces and the wide traversal's stack
+ *     capacity and bound (the topology, and with it the worst-case stack, is unchanged).
+ *   - cfg.wide 1 (default): the exact 4-wide array's planes are copied from the refitted
+ *     Compact2 slots the bind-time collapse took them from (the collapse is not redone:
+ *     refitted surface areas would choose other children). cfg.wide 2: the quantized array
+ *     has no in-place update; it is derived again from the refitted nodes through the
+ *     bind-time host path, which makes the call SYNCHRONOUS and slow (results are correct).
+ * MRT_ERR_NOT_BOUND before a bind; MRT_ERR_INVALID_ARG when the bound nodes are not a tree
+ * (a child ref outside the array, a record reached twice or never). */
+int  mrt_tracer_refit(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,
+                      int64_t numTriangles, void* stream);
+
+/* Blocking (waits for the device): the plan's levels and bytes, the last refit's launches,
+ * and the out-of-range references skipped since the previous call (reset by it). All zero
+ * before the first refit after a bind / set_config. */
+int  mrt_tracer_refit_info(mrt_tracer* t, mrt_refit_info* info);
+
+/* Blocking debug copy-out of the derived 4-wide array (device -> host), e.g. after a
+ * refit: *bytes = its size (0 with cfg.wide 0); copied to out when out != NULL and
+ * capacity suffices (else MRT_ERR_TOO_LARGE). mrt_tracer_bind_info tells its format. */
+int  mrt_tracer_copy_wide_nodes(mrt_tracer* t, void* out, int64_t capacity, int64_t* bytes);
+
+/* Host-only (no device): the refit plan of a Compact2 node array (host memory), as the
+ * tracer builds it (csrc/refit_plan.cpp). order (nodeBytes / 64 entries, may be NULL): every
+ * node once, grouped by height — a node whose children are both leaves has height 0, any
+ * other 1 + the largest height of its inner children — level h at [levelOffsets[h],
+ * levelOffsets[h + 1]) (*numLevels + 1 entries; levelCapacity = entries levelOffsets holds,
+ * MRT_ERR_TOO_LARGE when too few; may be NULL). wideSrc (may be NULL): for the exact 4-wide
+ * form, four entries per wide node, binaryNode * 2 + side = the Compact2 slot whose box
+ * that wide child copies, -1 for an absent child, from the same collapse as
+ * mrt_derive_wide_nodes form 1; *numWideSrc (may be NULL: no map) = its entries. Any valid
+ * tree is accepted, whatever its numbering; MRT_ERR_INVALID_ARG for a child ref outside the
+ * array, a record reached twice or a record not reachable from node 0. */
+int  mrt_refit_plan(const void* nodes, int64_t nodeBytes, int32_t* order, int64_t* levelOffsets, int32_t levelCapacity,
+                    int32_t* numLevels, int32_t* wideSrc, int64_t wideSrcCapacity, int64_t* numWideSrc);
 
 /* Host-only (no device): the 4-wide node array a tracer derives at bind time
  * from a Compact2 node array (host memory). form 1 = exact child boxes, 128 B per

@@ -92,6 +92,19 @@ void mrth_bvh_destroy(mrth_bvh* b);
 int  mrth_bvh_buffers(const mrth_bvh* b, const void** nodes, int64_t* nodeBytes, const void** woop,
                       int64_t* woopBytes, const int32_t** triIndex, int64_t* triIndexBytes);
 int  mrth_bvh_get_stats(const mrth_bvh* b, mrth_bvh_stats* out);
+/* Refit in place for moved vertices of the same topology (no reference counterpart; the
+ * CPU statement of mrt_tracer_refit, mrt.h). triangles are the ones the BVH was built over
+ * (triIndex refers to them), vertices their new positions. Every leaf is walked from its
+ * first Woop slot in steps of three up to its terminator: its Woop rows are rewritten from
+ * triIndex -> triangle -> vertices, its box becomes the min/max of its triangles' vertices
+ * (the whole triangle also where the SBVH builder had clipped the reference, so a refitted
+ * box may be looser than the built one, never tighter than the geometry); every inner box
+ * becomes the union of its child's two boxes. Words 12-15 of the nodes, triIndex and the
+ * terminators are untouched; an empty leaf keeps its box and adds nothing to its ancestors.
+ * A triIndex entry >= numTriangles, or a vertex index outside [0, numVertices), is
+ * MRTH_ERR_INVALID_ARG and nothing is written. */
+int  mrth_bvh_refit(mrth_bvh* b, const float* vertices, int64_t numVertices, const int32_t* triangles,
+                    int64_t numTriangles);
 /* Woop rows (Z,U,V; 12 floats) of one triangle, CudaBVH::woopifyTri. */
 void mrth_woopify(const float v0[3], const float v1[3], const float v2[3], float out[12]);
 
