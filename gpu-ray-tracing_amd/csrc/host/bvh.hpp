@@ -75,6 +75,20 @@ void woopify(const Vec3f& v0, const Vec3f& v1, const Vec3f& v2, Vec4f out[3]);
 bool refit_compact2(Compact2& c, const float* vertices, int64_t numVertices, const int32_t* triangles,
                     int64_t numTriangles, std::string* err);
 
+// A linear BVH built straight into Compact2 buffers (lbvh.cpp; no reference counterpart;
+// the CPU statement of the device build, csrc/lbvh_kernel.hip): triangles in Morton order
+// of their box centres, the Karras hierarchy over the sorted keys, a node kept as a record
+// iff it holds more than maxLeaf (1..8) triangles, boxes and Woop rows by refit_compact2.
+// No spatial splits and no SAH: a tree of lower quality than build_sbvh's, in a fraction of
+// its time. False for maxLeaf out of range or a vertex index out of range.
+struct LbvhStats {
+    int64_t records = 0;   // 64-byte node records
+    int64_t leaves = 0;    // the one-record tree's empty leaf included
+    int64_t slots = 0;     // Woop slots = triIndex entries: 3 * triangles + leaves
+};
+bool build_lbvh(const float* vertices, int64_t numVertices, const int32_t* triangles, int64_t numTriangles,
+                int maxLeaf, Compact2& out, LbvhStats* stats, std::string* err);
+
 // bvhcache .dat: S32 layout, then per buffer S64 byte count + bytes, little
 // endian (CudaBVH.cc:79-97,113-116; Buffer.cc:327-360). Layout 5 = Compact2.
 bool save_dat(const std::string& path, const Compact2& c, std::string* err);

@@ -211,6 +211,29 @@ int mrth_bvh_build(const mrth_scene* s, const mrth_build_params* p, mrth_bvh** o
     }
 }
 
+int mrth_bvh_build_lbvh(const mrth_scene* s, int32_t max_leaf_size, mrth_bvh** out) {
+    if (!s || !out) return fail(MRTH_ERR_INVALID_ARG, "null argument");
+    if (max_leaf_size == 0) max_leaf_size = MRTH_LBVH_DEFAULT_MAX_LEAF;
+    try {
+        auto b = std::make_unique<mrth_bvh>();
+        const mrt::Scene& sc = s->scene;
+        static_assert(sizeof(mrt::Vec3i) == 12 && sizeof(mrt::Vec3f) == 12, "Scene buffers are packed 12-byte records");
+        mrt::LbvhStats st;
+        std::string err;
+        if (!mrt::build_lbvh(reinterpret_cast<const float*>(sc.vertices.data()), (int64_t)sc.vertices.size(),
+                             reinterpret_cast<const int32_t*>(sc.triangles.data()), (int64_t)sc.triangles.size(),
+                             max_leaf_size, b->c2, &st, &err))
+            return fail(MRTH_ERR_INVALID_ARG, err);
+        b->stats.inner_nodes = st.records;
+        b->stats.leaf_nodes = st.leaves;
+        b->stats.tri_refs = (int64_t)sc.triangles.size();
+        *out = b.release();
+        return MRTH_OK;
+    } catch (const std::exception& e) {
+        return fail(MRTH_ERR_GENERATOR, std::string("build failed: ") + e.what());
+    }
+}
+
 int mrth_bvh_load(const char* path, mrth_bvh** out) {
     if (!path || !out) return fail(MRTH_ERR_INVALID_ARG, "null argument");
     auto b = std::make_unique<mrth_bvh>();

@@ -28,7 +28,10 @@ MRT_TRACE_STATS = 1 << 3
 MRT_TRACE_SECONDARY = 1 << 4
 MRT_ERR_INVALID_ARG = 1
 MRT_ERR_NOT_BOUND = 2
+MRT_ERR_HIP = 3
+MRT_ERR_TOO_LARGE = 5
 MRT_ERR_STACK_OVERFLOW = 6
+MRT_LBVH_DEFAULT_MAX_LEAF = 4
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -53,6 +56,16 @@ class BindInfo(C.Structure):
 
 class RefitInfo(C.Structure):
     _fields_ = [("levels", i32), ("launches", i32), ("plan_bytes", i64), ("skipped_refs", i64)]
+
+
+class LbvhParams(C.Structure):
+    _fields_ = [("max_leaf_size", i32)]
+
+
+class BuildInfo(C.Structure):
+    _fields_ = [("wall_ms", C.c_double), ("plan_ms", C.c_double), ("bind_ms", C.c_double), ("sort_ms", f32),
+                ("emit_ms", f32), ("fit_ms", f32), ("levels", i32), ("records", i64), ("leaves", i64), ("slots", i64),
+                ("scratch_bytes", i64), ("skipped_refs", i64), ("max_leaf_size", i32)]
 
 
 class TunedSchedule(C.Structure):
@@ -93,6 +106,10 @@ TRACE_SYMBOLS = [
     ("mrt_tracer_stack_overflows", i32, [vp, C.POINTER(i64), i32]),
     ("mrt_tracer_refit", i32, [vp, vp, i64, vp, i64, vp]),
     ("mrt_tracer_refit_info", i32, [vp, C.POINTER(RefitInfo)]),
+    ("mrt_lbvh_sizes", i32, [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    ("mrt_tracer_build", i32, [vp, vp, i64, vp, i64, C.POINTER(LbvhParams), vp, i64, vp, i64, vp, i64, C.POINTER(i64),
+                               C.POINTER(i64), C.POINTER(i64), vp]),
+    ("mrt_tracer_build_info", i32, [vp, C.POINTER(BuildInfo)]),
     ("mrt_tracer_copy_wide_nodes", i32, [vp, vp, i64, C.POINTER(i64)]),
     ("mrt_refit_plan", i32, [vp, i64, vp, vp, i32, C.POINTER(i32), vp, i64, C.POINTER(i64)]),
     ("mrt_derive_wide_nodes", i32, [vp, i64, vp, i64, i32, vp, i64, C.POINTER(i64)]),
@@ -138,6 +155,7 @@ HOST_SYMBOLS = [
     ("mrth_scene_hash", u32, [vp]),
     ("mrth_bvh_cache_name", i32, [vp, C.POINTER(BuildParams), C.c_char_p]),
     ("mrth_bvh_build", i32, [vp, C.POINTER(BuildParams), C.POINTER(vp)]),
+    ("mrth_bvh_build_lbvh", i32, [vp, i32, C.POINTER(vp)]),
     ("mrth_bvh_load", i32, [C.c_char_p, C.POINTER(vp)]),
     ("mrth_bvh_save", i32, [vp, C.c_char_p]),
     ("mrth_bvh_from_buffers", i32, [vp, i64, vp, i64, vp, i64, C.POINTER(vp)]),

@@ -305,6 +305,78 @@ int  mrt_tracer_refit_info(mrt_tracer* t, mrt_refit_info* info);
  * capacity suffices (else MRT_ERR_TOO_LARGE). mrt_tracer_bind_info tells its format. */
 int  mrt_tracer_copy_wide_nodes(mrt_tracer* t, void* out, int64_t capacity, int64_t* bytes);
 
+/* ---- device build (linear BVH) ------------------------------------------- */
+/* Parameters of mrt_tracer_build (NULL = defaults). */
+typedef struct mrt_build_params {
+    int32_t max_leaf_size;     /* triangles per leaf at most: 1..8; 0 = default (MRT_LBVH_DEFAULT_MAX_LEAF) */
+} mrt_build_params;
+enum { MRT_LBVH_DEFAULT_MAX_LEAF = 4 };
+
+/* What mrt_tracer_build_info reports about the last successful build. */
+typedef struct mrt_build_info {
+    double  wall_ms;           /* the whole call                                                        */
+    double  plan_ms;           /* host: the emitted nodes copied back, the level plan, its upload       */
+    double  bind_ms;           /* host: the bind (the 4-wide collapse, cfg.wide)                        */
+    float   sort_ms;           /* device (events): centroid bounds, keys, the sort                      */
+    float   emit_ms;           /* device: hierarchy, flags, prefix sums, emission                       */
+    float   fit_ms;            /* device: Woop rows and boxes (the refit launches)                      */
+    int32_t levels;            /* height levels of the tree (mrt_refit_info.levels)                     */
+    int64_t records;           /* 64-byte node records written                                          */
+    int64_t leaves;            /* leaves (the one-record tree's empty leaf included)                    */
+    int64_t slots;             /* Woop slots = triIndex entries written: 3 * triangles + leaves         */
+    int64_t scratch_bytes;     /* stream-ordered scratch taken and returned by the call                 */
+    int64_t skipped_refs;      /* triangles with a vertex index out of range: zeroed rows, in no box    */
+    int32_t max_leaf_size;     /* the value the build used                                              */
+} mrt_build_info;
+
+/* Host-only: upper bounds of what a build of numTriangles writes, the capacities
+ * mrt_tracer_build asks for: numTriangles - 1 node records (at least one) of 64 bytes,
+ * 4 * numTriangles + 1 Woop slots of 16 bytes, one triIndex int per slot.
+ * MRT_ERR_INVALID_ARG for numTriangles < 1 or a null output, MRT_ERR_TOO_LARGE above the
+ * refit's limits (2^28 slots: 67 108 863 triangles). */
+int  mrt_lbvh_sizes(int64_t numTriangles, int64_t* nodeBytes, int64_t* woopBytes, int64_t* triIndexBytes);
+
+/* Build a linear BVH on the device from vertices (3 floats each) and triangles (3 vertex
+ * indices each), both DEVICE pointers, straight into the caller's Compact2 buffers nodes /
+ * woop / triIndex (DEVICE pointers, borrowed as with mrt_tracer_bind; capacities in bytes, at
+ * least mrt_lbvh_sizes), fill boxes and Woop rows, and bind the result: later traces and
+ * refits work as after mrt_tracer_bind. *nodeBytes / *woopBytes / *triIndexBytes (host) = the
+ * bytes written and bound. No reference counterpart (the reference builds on the CPU).
+ *   - The tree: triangles sorted (stable, equal keys in index order) by the 63-bit Morton
+ *     code of their box centres quantized to 21 bits per axis over the centres' bounds; the
+ *     Karras 2012 hierarchy over the sorted keys (equal codes split by the bits of their
+ *     sorted positions); a node is kept as a record iff it holds more than max_leaf_size
+ *     triangles, a smaller child range is a leaf. Records are numbered in Karras order (the
+ *     root is record 0), leaves by sorted position: the leaf of rank r starting at sorted
+ *     position p owns Woop slots 3p + r onwards, its terminator included. At most
+ *     max_leaf_size triangles give one record whose second child is an empty leaf with the
+ *     first child's box. Boxes and Woop rows are what mrt_tracer_refit computes; the bytes
+ *     equal mrth_bvh_build_lbvh's (mrt_host.h) and do not vary between runs.
+ *   - Limits: the quality is below the SBVH's (no spatial splits, no SAH): traces are slower
+ *     than on a mrth_bvh_build tree (DESIGN §10 has the measured ratio). Coincident centres
+ *     split by index bits, so the depth can exceed 63: the per-lane binary order
+ *     (MRT_TRACE_LOCKSTEP_OFF, cfg.wide 0) then reports MRT_ERR_STACK_OVERFLOW as for any deep
+ *     tree, while the wide orders size their stack at bind.
+ *   - A triangle with a vertex index outside [0, numVertices) gets key 0, its vertices are
+ *     never read, its Woop rows stay zero (no ray hits it), it is in no box, and it is counted
+ *     (mrt_build_info.skipped_refs).
+ *   - SYNCHRONOUS: the launches run on `stream` (a hipStream_t, NULL = the null stream), but
+ *     the level plan of the emitted nodes is made on the host and the bind collapses them
+ *     there too, so the call returns after the device has finished. Scratch (about 75 bytes
+ *     per triangle) is taken and returned on the stream (hipMallocAsync / hipFreeAsync; a
+ *     failed allocation is MRT_ERR_HIP).
+ * Scalar arguments are checked first: MRT_ERR_INVALID_ARG for numTriangles < 1, numVertices
+ * < 0 or max_leaf_size outside 0..8; MRT_ERR_TOO_LARGE for more triangles than mrt_lbvh_sizes
+ * takes; then MRT_ERR_INVALID_ARG for a null pointer and MRT_ERR_TOO_LARGE for a capacity
+ * below mrt_lbvh_sizes. In all these cases nothing is written and the previous bind stands. */
+int  mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,
+                      int64_t numTriangles, const mrt_build_params* params, void* nodes, int64_t nodeCapacity,
+                      void* woop, int64_t woopCapacity, int32_t* triIndex, int64_t triIndexCapacity,
+                      int64_t* nodeBytes, int64_t* woopBytes, int64_t* triIndexBytes, void* stream);
+
+/* The last successful mrt_tracer_build of this handle (all zero before one). */
+int  mrt_tracer_build_info(mrt_tracer* t, mrt_build_info* info);
+
 /* Host-only (no device): the refit plan of a Compact2 node array (host memory), as the
  * tracer builds it (csrc/refit_plan.cpp). order (nodeBytes / 64 entries, may be NULL): every
  * node once, grouped by height — a node whose children are both leaves has height 0, any

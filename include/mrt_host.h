@@ -84,6 +84,16 @@ uint32_t mrth_scene_hash(const mrth_scene* s);
  * written to out (>= 13 bytes; 16 are touched). p NULL = defaults (mrth_default_build_params). */
 int  mrth_bvh_cache_name(const mrth_scene* s, const mrth_build_params* p, char out[16]);
 int  mrth_bvh_build(const mrth_scene* s, const mrth_build_params* p /* NULL = defaults */, mrth_bvh** out);
+/* A linear BVH (no reference counterpart; the CPU statement of mrt_tracer_build, mrt.h, whose
+ * bytes it reproduces): triangles sorted by the 63-bit Morton code of their box centres (a
+ * stable sort, equal codes in index order), the Karras 2012 hierarchy over the sorted keys,
+ * a node kept as a record iff it holds more than max_leaf_size triangles (1..8; 0 = the
+ * default, MRTH_LBVH_DEFAULT_MAX_LEAF), boxes and Woop rows as mrth_bvh_refit computes them.
+ * Single-threaded and deterministic. No spatial splits and no SAH: traces are slower than on
+ * mrth_bvh_build's tree, the build is orders of magnitude faster. stats: inner_nodes =
+ * records, leaf_nodes = leaves, tri_refs = triangles; the rest 0. */
+enum { MRTH_LBVH_DEFAULT_MAX_LEAF = 4 };
+int  mrth_bvh_build_lbvh(const mrth_scene* s, int32_t max_leaf_size, mrth_bvh** out);
 int  mrth_bvh_load(const char* datPath, mrth_bvh** out);
 int  mrth_bvh_save(const mrth_bvh* b, const char* datPath);
 int  mrth_bvh_from_buffers(const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
