@@ -1,0 +1,57 @@
+// launch_plan.hpp — the grid, the residency cap and the spill slab of a trace launch.
+// Plain C++ with no HIP in it (like tune.hpp): mrt_api.cpp feeds it the device's and the
+// kernel's figures, tests/cpp/launch_plan_driver.cpp runs it on the CPU.
+//
+// Two kinds of grid. The persistent one holds as many workgroups as are resident at once;
+// each takes numRays / gridLanes static rounds. The backfilled one (cfg.backfill = k) is
+// sized from the batch: every lane takes at most k rays, a workgroup ends after its k
+// rounds and the hardware workgroup dispatcher starts the next one in the freed slot, so
+// a tile of expensive rays holds its slot for its own duration only. How many workgroups
+// share a CU is then no longer set by the grid; dynamic LDS passed at launch caps it.
+//
+// An oversubscribed grid must never run code in which one workgroup waits for another:
+// the workgroup waited for may not be resident yet. The static strided rounds
+// (num_queues = -1) have no such wait, and the plan is made for them only (valid_cfg
+// refuses a backfill with queues or with the ray sort).
+#pragma once
+
+#include <cstdint>
+
+namespace mrt {
+
+constexpr int kMaxBackfill = 64;         // rays per lane a backfilled grid may be sized for
+// Most bytes of a backfilled launch's spill slab, per workspace: the slab holds
+// (stackCap - S) ints per launched lane, and a launched grid grows with the batch.
+constexpr int64_t kSpillCapBytes = 256ll << 20;
+
+struct LaunchPlanIn {
+    int numRays = 0;
+    int backfill = 0;        // 0: the persistent grid; 1..kMaxBackfill: rays per lane
+    int numCUs = 1;
+    int blockThreads = 256;  // threads per workgroup (trace_kernel.hpp kBlockThreads), a multiple of 64
+    int wavesPerCU = 0;      // resident waves per CU asked for (> 0)
+    int staticLds = 0;       // the kernel's static LDS bytes per workgroup
+    int ldsPerCU = 0;        // LDS bytes of a CU
+    int occBlocks = 1;       // workgroups per CU the code object admits without dynamic LDS
+    int spillEntries = 0;    // stackCap - S: spill-slab ints per lane
+    int64_t spillCapBytes = kSpillCapBytes;
+};
+
+struct LaunchPlan {
+    int blocks = 0;          // workgroups launched
+    int backfill = 0;        // rays per lane the grid was sized for (>= the asked k); 0: persistent
+    int blocksPerCU = 0;     // workgroups resident per CU
+    int dynLds = 0;          // dynamic LDS bytes per workgroup (the residency cap); 0: none needed
+    int64_t spillInts = 0;   // spillEntries * launched lanes
+};
+
+// Workgroups per CU of a launch asked for wavesPerCU waves on a code object admitting occBlocks.
+int plan_blocks_per_cu(int wavesPerCU, int occBlocks, int blockThreads = 256);
+// Workgroups of a grid whose lanes take at most k rays each, a multiple of 8 (one XCD group each).
+int64_t backfill_blocks(int64_t numRays, int k, int blockThreads = 256);
+// Dynamic LDS bytes with which exactly `blocks` workgroups of staticLds static bytes fit a CU's
+// ldsPerCU; -1 when no size does (the static bytes alone admit fewer).
+int cap_dyn_lds(int blocks, int staticLds, int ldsPerCU);
+LaunchPlan plan_launch(const LaunchPlanIn& in);
+
+}  // namespace mrt

@@ -17,6 +17,7 @@
 
 #include "../../include/mrt.h"
 #include "lbvh_common.hpp"
+#include "launch_plan.hpp"
 #include "lbvh_kernel.hpp"
 #include "refit_kernel.hpp"
 #include "refit_plan.hpp"
@@ -36,6 +37,8 @@ struct mrt_tracer {
     int device = 0;
     int numCUs = 0;
     int numXccs = 1;   // XCDs of the device (partition): the per-XCD queue candidate's queue count
+    int ldsPerCU = 0;  // LDS bytes of a CU (the device attribute; 0: unknown, no backfilled launches)
+    int ldsPerBlock = 0;   // most LDS bytes one workgroup may hold
     std::mutex mu;
 
     // Bound Compact2 BVH (borrowed device pointers).
@@ -96,6 +99,12 @@ struct mrt_tracer {
     // Occupancy per kernel variant (index variant_key(), below 256), queried once
     // (hipOccupancy* is a host round-trip that would otherwise sit on every launch).
     int occ[512] = {};
+    // Backfilled launches (launch_plan.hpp): per variant and residency cap of 1..kMaxCapBlocks
+    // workgroups per CU, the dynamic LDS bytes + 1 that the occupancy query confirmed to give
+    // exactly that residency (0: not asked yet, -1: none found, such launches run persistent).
+    static constexpr int kMaxCapBlocks = 8;
+    int capDyn[512][kMaxCapBlocks + 1] = {};
+    int staticLds[512] = {};   // per variant: the kernel's static LDS bytes + 1 (0: not asked yet)
 
     // cfg.autotune: per (batch size, variant) the ray-distribution schedule the
     // measured launches chose (tune.cpp), reset on bind/set_config.
@@ -183,7 +192,7 @@ constexpr int kDefaultAutotune = 1;
 
 mrt_launch_cfg default_cfg() {
     mrt_launch_cfg c;
-    c.waves_per_cu = 0;   // auto: sized from the batch (grid_blocks)
+    c.waves_per_cu = 0;   // auto: sized from the batch (grid_waves_per_cu)
     c.fetch_threshold = 0;   // strided mode: a wave refills once all its lanes are done
     c.num_queues = -1;       // static strided assignment (see trace_kernel.hip); 1..8 = atomic queues
     c.lds_stack = 16;
@@ -197,6 +206,7 @@ mrt_launch_cfg default_cfg() {
     c.queue_block = 0;
     c.ray_sort = 0;
     c.queue_xcc_mask = 0;
+    c.backfill = 0;          // the persistent grid
     return c;
 }
 
@@ -210,7 +220,11 @@ bool valid_cfg(const mrt_launch_cfg& c) {
            c.tail_lanes >= 0 && c.tail_lanes <= 16 &&
            c.queue_shared >= 0 && c.queue_shared <= 100 && c.queue_block >= 0 && c.queue_block <= (1 << 20) &&
            (c.queue_block & (c.queue_block - 1)) == 0 && (c.queue_block == 0 || c.queue_block >= 64) &&
-           c.queue_xcc_mask >= 0 && c.queue_xcc_mask <= 15 && (c.ray_sort == 0 || c.ray_sort == 1);
+           c.queue_xcc_mask >= 0 && c.queue_xcc_mask <= 15 && (c.ray_sort == 0 || c.ray_sort == 1) &&
+           c.backfill >= 0 && c.backfill <= mrt::kMaxBackfill &&
+           // a backfilled grid is oversubscribed: only the static rounds, in which no workgroup waits for
+           // another (the queues' unserved-queue sweep does), and not the one-round ray sort
+           (c.backfill == 0 || (c.num_queues < 0 && c.ray_sort == 0));
 }
 
 // The frontier tail runs in the exact 4-wide kernels whose leaf refs carry counts.
@@ -251,12 +265,15 @@ int variant_key(const mrt::TraceVariant& v) {
            (v.nodes << 6) | (v.tail ? 256 : 0);   // < 512 = the size of mrt_tracer::occ
 }
 
-// Persistent grid: as many 256-thread workgroups per CU as the config asks for
-// (or the batch size suggests) and the code object's occupancy admits; every
-// workgroup is resident at once.
-int grid_blocks(mrt_tracer* t, const mrt_launch_cfg& cfg, const mrt::TraceVariant& v, int numRays, int* outBlocksPerCU) {
+// Workgroups per CU the code object of a variant admits (queried once).
+int variant_occupancy(mrt_tracer* t, const mrt::TraceVariant& v) {
     int& occ = t->occ[variant_key(v)];
     if (occ <= 0 && (mrt::trace_occupancy(v, &occ) != hipSuccess || occ <= 0)) occ = 1;
+    return occ;
+}
+
+// Waves per CU a launch asks for: the configuration's, or what the batch size suggests.
+int grid_waves_per_cu(const mrt_tracer* t, const mrt_launch_cfg& cfg, int numRays) {
     int waves = cfg.waves_per_cu;
     if (waves == 0 && cfg.num_queues < 0) {
         // Static strided assignment: 28 waves/CU (7 workgroups) measured best or
@@ -273,11 +290,66 @@ int grid_blocks(mrt_tracer* t, const mrt_launch_cfg& cfg, const mrt::TraceVarian
             waves = (int)std::min<long long>(32, std::max<long long>(kAutoMinWaves, (lanesPerCU + 63) / 64));
         }
     }
-    constexpr int wavesPerBlock = mrt::kBlockThreads / 64;
-    const int want = std::max(1, (waves + wavesPerBlock - 1) / wavesPerBlock);
-    const int perCU = std::min(want, occ);
-    if (outBlocksPerCU) *outBlocksPerCU = perCU;
-    return perCU * t->numCUs;
+    return waves;
+}
+
+static_assert(mrt::kTuneMaxBackfill == mrt::kMaxBackfill, "tune.hpp restates launch_plan.hpp's kMaxBackfill");
+
+// The dynamic LDS with which exactly perCU workgroups of variant v are resident per CU, confirmed
+// by the occupancy query once per (variant, perCU); -1 when no size is confirmed. The arithmetic
+// (cap_dyn_lds) proposes, the query decides: a disagreement is repaired by stepping the size, and
+// a launch never runs at a residency nobody confirmed.
+int confirmed_cap_lds(mrt_tracer* t, const mrt::TraceVariant& v, int perCU, int staticLds, int proposed) {
+    if (perCU < 1 || perCU > mrt_tracer::kMaxCapBlocks) return -1;
+    int& slot = t->capDyn[variant_key(v)][perCU];
+    if (slot != 0) return slot > 0 ? slot - 1 : -1;
+    slot = -1;
+    constexpr int kStep = 1024, kMaxSteps = 32;
+    int dyn = proposed;
+    for (int i = 0; i < kMaxSteps && dyn >= 0 && staticLds + dyn <= std::min(t->ldsPerCU, t->ldsPerBlock); i++) {
+        // above 64 KB a launch needs the function's dynamic-LDS limit raised first
+        if (staticLds + dyn > (64 << 10) && mrt::trace_allow_dynamic_lds(v, dyn) != hipSuccess) break;
+        int got = 0;
+        if (mrt::trace_occupancy(v, &got, dyn) != hipSuccess) break;
+        if (got == perCU) {
+            slot = dyn + 1;
+            return dyn;
+        }
+        dyn += got > perCU ? kStep : -kStep;
+    }
+    (void)hipGetLastError();   // a refused query leaves no sticky error behind
+    return -1;
+}
+
+// The launch's grid (launch_plan.hpp): the persistent one — as many 256-thread workgroups per CU
+// as the config asks for (or the batch size suggests) and the code object's occupancy admits,
+// every workgroup resident at once — or, with cfg.backfill, one sized from the batch.
+mrt::LaunchPlan launch_plan(mrt_tracer* t, const mrt_launch_cfg& cfg, const mrt::TraceVariant& v, int numRays, int stackCap) {
+    mrt::LaunchPlanIn in;
+    in.numRays = numRays;
+    in.numCUs = t->numCUs;
+    in.blockThreads = mrt::kBlockThreads;
+    in.wavesPerCU = grid_waves_per_cu(t, cfg, numRays);
+    in.occBlocks = variant_occupancy(t, v);
+    in.spillEntries = stackCap - v.ldsStack;
+    in.ldsPerCU = t->ldsPerCU;
+    mrt::LaunchPlan persistent = mrt::plan_launch(in);
+    if (cfg.backfill <= 0 || cfg.num_queues >= 1 || t->ldsPerCU <= 0) return persistent;
+    int& lds = t->staticLds[variant_key(v)];
+    if (lds == 0) {   // from the function's attributes, once per variant (a host round trip)
+        hipFuncAttributes attr{};
+        if (mrt::trace_kernel_attributes(v, &attr) != hipSuccess) return persistent;
+        lds = (int)attr.sharedSizeBytes + 1;
+    }
+    in.backfill = cfg.backfill;
+    in.staticLds = lds - 1;
+    mrt::LaunchPlan p = mrt::plan_launch(in);
+    if (p.backfill > 0 && p.dynLds > 0) {
+        const int dyn = confirmed_cap_lds(t, v, p.blocksPerCU, in.staticLds, p.dynLds);
+        if (dyn < 0) return persistent;
+        p.dynLds = dyn;
+    }
+    return p;
 }
 
 // Waits for the last launch that used `w` without touching the stream it ran on (the
@@ -548,15 +620,15 @@ mrt::TraceArgs trace_args(const mrt_tracer* t, const mrt_launch_cfg& cfg, const 
 
 // Enqueues the launch on s: inside the blocking call's event pair (evStart .. evStop) when
 // `blocking`, and inside the autotuner's (tuneStart, tuneStop) when it times this launch.
-int enqueue_trace(mrt_tracer* t, const mrt::TraceVariant& v, const mrt::TraceArgs& a, int blocks, mrt::Workspace* ws,
-                  hipStream_t s, bool blocking, hipEvent_t tuneStart, hipEvent_t tuneStop) {
+int enqueue_trace(mrt_tracer* t, const mrt::TraceVariant& v, const mrt::TraceArgs& a, int blocks, int dynLds,
+                  mrt::Workspace* ws, hipStream_t s, bool blocking, hipEvent_t tuneStart, hipEvent_t tuneStop) {
     // Queue heads restart at zero for every launch; strided mode has none.
     if (a.numQueues > 0)
         MRT_HIP(hipMemsetAsync(ws->queues, 0, mrt::kQueueLines * mrt::kQueueStrideWords * sizeof(unsigned), s));
     if (blocking) MRT_HIP(hipMemsetAsync(ws->status + mrt::kTimedSlot, 0, sizeof(int), s));
     if (blocking) MRT_HIP(hipEventRecord(t->evStart, s));
     if (tuneStart) MRT_HIP(hipEventRecord(tuneStart, s));
-    MRT_HIP(mrt::launch_trace(v, a, blocks, s));
+    MRT_HIP(mrt::launch_trace(v, a, blocks, s, dynLds));
 #ifdef MRT_DONE_EVENT
     MRT_HIP(hipEventRecord(ws->done, s));
 #endif
@@ -613,10 +685,10 @@ int trace_impl(mrt_tracer* t, const void* rays, void* results, int32_t numRays, 
         cfg = mrt::tune_candidate(t->numXccs, cfg, cand, tune);
     }
     v.tail = with_tail(t, v, cfg);   // a tuned candidate may run without the tail
-    int perCU = 0;
-    const int blocks = grid_blocks(t, cfg, v, numRays, &perCU);
-    const int totalLanes = blocks * mrt::kBlockThreads;
     const int stackCap = v.nodes != mrt::kNodeCompact2 ? t->wideStackCap : mrt::kStackCapacity;
+    const mrt::LaunchPlan plan = launch_plan(t, cfg, v, numRays, stackCap);
+    const int blocks = plan.blocks;
+    const int totalLanes = blocks * mrt::kBlockThreads;
     mrt::Workspace* ws = nullptr;
     if (int rc = workspace_for(t, stream, totalLanes, v.ldsStack, stackCap, &ws)) return rc;
 
@@ -624,12 +696,16 @@ int trace_impl(mrt_tracer* t, const void* rays, void* results, int32_t numRays, 
     a.rays = static_cast<const float4*>(rays);
     a.results = static_cast<int2*>(results);
     a.stats = reinterpret_cast<int4*>(stats);
-    if (int rc = enqueue_trace(t, v, a, blocks, ws, static_cast<hipStream_t>(stream), info != nullptr, tuneStart, tuneStop))
+    if (int rc = enqueue_trace(t, v, a, blocks, plan.dynLds, ws, static_cast<hipStream_t>(stream), info != nullptr,
+                               tuneStart, tuneStop))
         return rc;
     if (slot >= 0) tune->slot_started(slot, cand);
     if (!info) return MRT_OK;
     info->autotune_candidate = tune ? tune->info_code(cand) : -1;
     info->autotune_locked = tune && tune->locked >= 0 ? 1 : 0;
+    info->backfill = plan.backfill;
+    info->blocks_per_cu = plan.blocksPerCU;
+    info->dyn_lds_bytes = plan.dynLds;
     return fill_info(t, v, a, ws, info);
 }
 
@@ -944,6 +1020,11 @@ int mrt_tracer_create(int device, mrt_tracer** out) {
     t->device = device;
     t->numCUs = cus;
     t->numXccs = std::max(1, std::min(xccs, mrt::kMaxQueues));
+    int lds = 0;
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) == hipSuccess && lds > 0)
+        t->ldsPerCU = lds;
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && lds > 0)
+        t->ldsPerBlock = lds;
     t->cfg = default_cfg();
     *out = t;
     return MRT_OK;
@@ -1012,6 +1093,7 @@ int mrt_tracer_set_config(mrt_tracer* t, const mrt_launch_cfg* cfg) {
     if (c.queue_block < 0) c.queue_block = d.queue_block;
     if (c.queue_xcc_mask < 0) c.queue_xcc_mask = d.queue_xcc_mask;
     if (c.ray_sort < 0) c.ray_sort = d.ray_sort;
+    if (c.backfill < 0) c.backfill = d.backfill;
     if (!valid_cfg(c)) return fail(MRT_ERR_INVALID_ARG, "launch config out of range");
     std::lock_guard<std::mutex> lock(t->mu);
     t->cfg = c;

@@ -103,11 +103,17 @@ int64_t wide_stack_bound(const uint32_t* wide, int64_t numWide, int nodeWords);
 bool build_wide4q(const int32_t* nodes, int64_t numNodes, std::vector<uint32_t>* out, const int32_t* woopX = nullptr,
                   int64_t woopSlots = 0);
 
-// Launch one persistent trace. grid = number of 256-thread workgroups.
-hipError_t launch_trace(const TraceVariant& v, const TraceArgs& a, int gridBlocks, hipStream_t s);
+// Launch one trace. grid = number of 256-thread workgroups: all resident at once (the persistent
+// launch), or more (a backfilled static launch, launch_plan.hpp), then with dynLdsBytes of
+// dynamic LDS per workgroup, which no kernel reads: it only caps how many share a CU.
+hipError_t launch_trace(const TraceVariant& v, const TraceArgs& a, int gridBlocks, hipStream_t s, int dynLdsBytes = 0);
 
-// Resident 256-thread workgroups per CU for a variant (occupancy query).
-hipError_t trace_occupancy(const TraceVariant& v, int* blocksPerCU);
+// Resident 256-thread workgroups per CU for a variant (occupancy query) with dynLdsBytes of
+// dynamic LDS per workgroup.
+hipError_t trace_occupancy(const TraceVariant& v, int* blocksPerCU, int dynLdsBytes = 0);
+
+// Lets a variant be launched with up to dynLdsBytes of dynamic LDS (needed above 64 KB).
+hipError_t trace_allow_dynamic_lds(const TraceVariant& v, int dynLdsBytes);
 
 // Static facts about a variant's code object (for occupancy sizing/reporting).
 hipError_t trace_kernel_attributes(const TraceVariant& v, hipFuncAttributes* attr);

@@ -66,7 +66,8 @@ constexpr float kTuneMargin = 0.03f;
 
 mrt_launch_cfg effective_cfg(const mrt_launch_cfg& user, int numCUs, int64_t bvhBytes, int numRays) {
     mrt_launch_cfg c = user;
-    const bool defaults = c.num_queues < 0 && c.waves_per_cu == 0 && c.fetch_threshold == 0 && c.lane_groups == 1;
+    const bool defaults = c.num_queues < 0 && c.waves_per_cu == 0 && c.fetch_threshold == 0 && c.lane_groups == 1 &&
+                          c.backfill == 0;   // a backfilled grid runs the static rounds only
     if (defaults && bvhBytes > kMallBytes) {
         const int64_t lanes16 = (int64_t)std::max(1, numCUs) * kBigQueueWaves * 64;
         c.num_queues = 1;
@@ -80,14 +81,32 @@ int rule_candidate(const mrt_launch_cfg& rule) {
     return rule.num_queues == 1 ? (rule.waves_per_cu == kBigQueueWaves ? 3 : 4) : 0;
 }
 
+namespace {
+mrt_launch_cfg explored_candidate(int numXccs, const mrt_launch_cfg& base, int c, const TuneState* st);
+}
+
 mrt_launch_cfg tune_candidate(int numXccs, const mrt_launch_cfg& base, int c, const TuneState* st) {
+    mrt_launch_cfg x = explored_candidate(numXccs, base, c, st);
+    if (st && st->backfill > 0 && st->locked >= 0 && c == st->locked) {
+        // a saved schedule with a backfilled grid (imported; static schedules only): the locked
+        // candidate's configuration with the grid sized for `backfill` rays per lane and, with a
+        // cap, that many workgroups resident per CU
+        x.backfill = st->backfill;
+        if (st->capBlocks > 0) x.waves_per_cu = 4 * st->capBlocks;
+    }
+    return x;
+}
+
+namespace {
+// The configuration of a candidate the exploring stages reach.
+mrt_launch_cfg explored_candidate(int numXccs, const mrt_launch_cfg& base, int c, const TuneState* st) {
     int sched = c, k = -1;
     if (st) st->decode(c, &sched, &k);
     if (k >= 0) {
         // stage 2/3: a schedule with the wave turning to its leaves once <= 4 (6)
         // lanes still search, with the frontier tail toggled, or with its lanes taking rays from 16
         // distant parts of each strided chunk (only for knobs the caller left at their defaults)
-        mrt_launch_cfg x = tune_candidate(numXccs, base, sched, nullptr);
+        mrt_launch_cfg x = explored_candidate(numXccs, base, sched, nullptr);
         if (k < 2 && base.spec_slack == kDefaultSpecSlack) x.spec_slack = k == 0 ? 4 : 6;
         if (k == 2 && base.tail_lanes == kDefaultTailLanes) x.tail_lanes = kDefaultTailLanes ? 0 : kTunedTailLanes;
         // lane groups mix a wave's rays from distant image regions: fewer waves hold a whole
@@ -138,6 +157,7 @@ mrt_launch_cfg tune_candidate(int numXccs, const mrt_launch_cfg& base, int c, co
     }
     return x;
 }
+}  // namespace
 
 TuneState::TuneState() { std::fill(slotCand, slotCand + kSlots, -1); }
 
@@ -176,7 +196,9 @@ int TuneState::info_code(int c) const {
 
 // candidate field: the locked candidate | the stage-1 winner << 8 (stage-2 candidates
 // are the stage-1 schedule with another speculation slack)
-int TuneState::export_code() const { return locked | (std::max(0, stage1) << 8); }
+int TuneState::export_code() const {
+    return locked | (std::max(0, stage1) << 8) | (backfill << kBackfillShift) | (capBlocks << kCapShift);
+}
 
 int TuneState::pick(int incumbent, int first, int last) const {
     int best = incumbent;
@@ -261,7 +283,7 @@ int TuneState::next_launch(int* slot) {
 TuneState* TuneTable::lookup(const mrt_launch_cfg& uc, const mrt_launch_cfg& rule, uint32_t flags, int numRays,
                              int variant, const void* stream) {
     if (!(uc.autotune && uc.num_queues < 0 && uc.waves_per_cu == 0 && uc.fetch_threshold == 0 && uc.lane_groups == 1 &&
-          !(flags & MRT_TRACE_STATS)))
+          uc.backfill == 0 && !(flags & MRT_TRACE_STATS)))
         return nullptr;
     // secondary rays (MRT_TRACE_SECONDARY) settle their own schedule: a diffuse batch of a primary
     // batch's size runs differently (round-5 README table: Mori primary 4829 Mrays/s on the diffuse
@@ -292,6 +314,8 @@ TuneState* TuneTable::lookup(const mrt_launch_cfg& uc, const mrt_launch_cfg& rul
             bestGap = gap;
             tune->stage1 = kv.second->stage1;
             tune->locked = kv.second->locked;
+            tune->backfill = kv.second->backfill;
+            tune->capBlocks = kv.second->capBlocks;
             tune->inherited = true;
         }
         tunes[key] = tune;
@@ -320,10 +344,16 @@ int TuneTable::export_schedules(mrt_tuned_schedule* out, int capacity) const {
 
 int TuneTable::import_schedules(const mrt_tuned_schedule* in, int count) {
     for (int i = 0; i < count; i++) {
-        const int locked = in[i].candidate & 0xff, stage1 = in[i].candidate >> 8;
+        const int code = in[i].candidate;
+        if (code < 0 || (code >> TuneState::kCodeBits) != 0) return MRT_ERR_INVALID_ARG;
+        const int locked = code & 0xff, stage1 = (code >> 8) & 0xff;
+        const int backfill = (code >> TuneState::kBackfillShift) & 0xff, cap = (code >> TuneState::kCapShift) & 7;
         if (in[i].version != MRT_TUNE_VERSION || in[i].num_rays <= 0 || locked >= TuneState::kSchedules + TuneState::kStage2 ||
-            stage1 < 0 || stage1 >= TuneState::kSchedules)
+            stage1 >= TuneState::kSchedules || backfill > kTuneMaxBackfill || (cap > 0 && backfill == 0))
             return MRT_ERR_INVALID_ARG;
+        // a backfilled grid is for the static schedules only: no workgroup of theirs waits for another
+        const int sched = locked < TuneState::kSchedules ? locked : stage1;
+        if (backfill > 0 && tune_candidate(1, mrt_launch_cfg{}, sched, nullptr).num_queues >= 1) return MRT_ERR_INVALID_ARG;
     }
     for (int i = 0; i < count; i++) {
         const auto key = std::make_pair((int)in[i].num_rays, (int)in[i].variant);
@@ -332,8 +362,10 @@ int TuneTable::import_schedules(const mrt_tuned_schedule* in, int count) {
             if ((int)tunes.size() >= kMaxTuned) return MRT_ERR_TOO_LARGE;
             it = tunes.emplace(key, new TuneState()).first;
         }
-        it->second->stage1 = in[i].candidate >> 8;
+        it->second->stage1 = (in[i].candidate >> 8) & 0xff;
         it->second->locked = in[i].candidate & 0xff;
+        it->second->backfill = (in[i].candidate >> TuneState::kBackfillShift) & 0xff;
+        it->second->capBlocks = (in[i].candidate >> TuneState::kCapShift) & 7;
         it->second->inherited = false;   // a schedule saved for this very key: exported again
     }
     return MRT_OK;

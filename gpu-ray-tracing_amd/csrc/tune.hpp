@@ -33,6 +33,7 @@ constexpr int kDefaultTailLanes = MRT_DEFAULT_TAIL_LANES;
 // is sized for exactly this occupancy.
 constexpr int kStridedWaves = 20;
 constexpr int kTuneMaxQueues = 8;    // trace_kernel.hpp kMaxQueues (mrt_api.cpp asserts it)
+constexpr int kTuneMaxBackfill = 64; // launch_plan.hpp kMaxBackfill (mrt_api.cpp asserts it)
 constexpr int kSecondaryKey = 512;   // tuning keys only: variant | kSecondaryKey for MRT_TRACE_SECONDARY batches
 
 // The launch configuration a trace uses (the fixed rule): the tracer's, except for a
@@ -77,6 +78,11 @@ struct TuneState {
     int s3mod = -1;      // its modifier k, tried on the schedules in s3sched (stage 3)
     int s3sched[kStage3] = {};
     int locked = -1;     // the chosen candidate (canonical: kSchedules + k of stage1), once settled
+    // A saved schedule's backfilled grid (launch_plan.hpp), reached by import only (the exploring
+    // stages never set them): rays per lane the grid is sized for (0: the persistent grid) and the
+    // residency cap in workgroups per CU (0: the schedule's own waves/CU). Static schedules only.
+    int backfill = 0;
+    int capBlocks = 0;
     const void* stream = nullptr;    // the stream this batch size was first launched on (only compared)
     bool multiStream = false;        // launched on several streams: not explored (settled schedule or the rule)
     bool inherited = false;          // took a nearby batch size's schedule (kTuneInherit): not exported
@@ -98,6 +104,9 @@ struct TuneState {
     // mrt_trace_info.autotune_candidate of a launch of candidate c; mrt_tuned_schedule.candidate once locked.
     int info_code(int c) const;
     int export_code() const;
+    // mrt_tuned_schedule.candidate: the locked candidate (bits 0-7), the schedule it modifies (8-15),
+    // the backfill k (16-23, at most kTuneMaxBackfill) and the residency cap (24-26); the rest zero.
+    static constexpr int kBackfillShift = 16, kCapShift = 24, kCodeBits = 27;
 
 private:
     int pick(int incumbent, int first, int last) const;

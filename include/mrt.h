@@ -152,12 +152,26 @@ typedef struct mrt_launch_cfg {
     int32_t queue_xcc_mask;    /* test hook, 0 = off (default; -1 = default): 1..15 = a wave takes from queue
                                   (XCC_ID & mask) % num_queues, so with mask 3 and 8 queues, queues 4..7
                                   have no waves of their own (the unserved-queue sweep must trace them) */
+    int32_t backfill;          /* static strided rounds only: 0 = the persistent grid (default; -1 = default):
+                                  every workgroup is resident for the whole launch and takes numRays /
+                                  grid lanes rounds. k = 1..64: the grid is sized from the batch so that
+                                  every lane takes at most k rays (ceil(numRays / (256 k)) workgroups,
+                                  rounded up to a multiple of 8); a workgroup ends after its rounds and the
+                                  hardware dispatcher starts the next one in the freed slot. waves_per_cu
+                                  then caps the workgroups resident per CU (dynamic LDS passed at launch,
+                                  checked against the occupancy query; 0 = the static default, 20). A batch
+                                  that fits the resident grid runs the persistent launch, and k is raised
+                                  until the spill slab (one per launched lane) fits 256 MB; mrt_trace_info
+                                  reports what a launch used. Refused with num_queues >= 1 and with
+                                  ray_sort = 1 (MRT_ERR_INVALID_ARG); a tracer with it set is not autotuned.
+                                  Results are unchanged: every ray is traced once either way           */
 } mrt_launch_cfg;
 
 /* Per-launch statistics reported back to the host (optional). */
 typedef struct mrt_trace_info {
     float   kernel_ms;         /* event-timed duration of the trace launch (if requested)        */
-    int32_t grid_waves;        /* persistent waves launched                                       */
+    int32_t grid_waves;        /* waves launched: all resident at once in a persistent launch; in a
+                                  backfilled one (backfill > 0) blocks_per_cu workgroups per CU at a time */
     int32_t block_threads;     /* threads per workgroup                                           */
     int32_t lds_stack_entries; /* per-lane traversal-stack entries held in LDS                    */
     int32_t wide;              /* node width the launch traversed: 2 (Compact2) or 4              */
@@ -176,6 +190,12 @@ typedef struct mrt_trace_info {
     int32_t stack_capacity;    /* stack entries (sentinel included) the launch had: 64 = the reference's
                                   for the binary order; the wide orders get the bound tree's worst case
                                   (never less than 64), so no ray of a tree overflows there          */
+    int32_t backfill;          /* rays per lane the launched grid was sized for (cfg.backfill or a saved
+                                  schedule's, raised where the spill slab asked for it); 0 = the persistent
+                                  grid, also for a batch that fits the resident grid                  */
+    int32_t blocks_per_cu;     /* workgroups resident per CU at once                                  */
+    int32_t dyn_lds_bytes;     /* dynamic LDS per workgroup that caps the residency of a backfilled
+                                  launch (0 = none needed, and in every persistent launch)            */
 } mrt_trace_info;
 
 /* What the last bind derived (mrt_tracer_bind_info). */
@@ -197,8 +217,11 @@ typedef struct mrt_bind_info {
 typedef struct mrt_tuned_schedule {
     int32_t num_rays;
     int32_t variant;
-    int32_t candidate;
-    int32_t version;           /* MRT_TUNE_VERSION when exported; others are refused on import */
+    int32_t candidate;         /* bits 0-15: the autotuner's code (mrt_trace_info.autotune_candidate);
+                                  bits 16-23: cfg.backfill of the schedule (static schedules only, 0..64);
+                                  bits 24-26: its residency cap in workgroups per CU (0 = the schedule's
+                                  own waves_per_cu); the bits above are zero                       */
+    int32_t version;          /* MRT_TUNE_VERSION when exported; others are refused on import */
 } mrt_tuned_schedule;
 enum { MRT_TUNE_VERSION = 11 };   /* 11: round 6 (schedules re-tuned on the round-6 library) */
 

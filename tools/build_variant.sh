@@ -15,10 +15,20 @@ else
     D=$REPO/gpu-ray-tracing_amd
 fi
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fgpu-flush-denormals-to-zero -ffp-contract=off -Wall -Wno-unused-result -I$D/../include"
-/opt/rocm/bin/hipcc $HIPFLAGS -fno-slp-vectorize $FLAGS -c $D/csrc/trace_kernel.hip -o $B/trace_kernel.o
-/opt/rocm/bin/hipcc $HIPFLAGS $FLAGS -c $D/csrc/raygen_kernel.hip -o $B/raygen_kernel.o
-OBJS="$B/trace_kernel.o $B/raygen_kernel.o"
-for src in $D/csrc/*.cpp; do   # mrt_api, tune, compat_api, wide_bvh (whichever the revision has)
+# every kernel file the revision has, with the Makefile's per-file flags: the traversal without SLP
+# vectorisation, the refit and LBVH kernels with IEEE denormals (they restate host arithmetic bit for bit)
+NOFTZ=${HIPFLAGS/-fgpu-flush-denormals-to-zero/}
+OBJS=""
+for src in $D/csrc/*.hip; do
+    k=$(basename $src .hip); obj=$B/$k.o
+    case $k in
+        trace_kernel) /opt/rocm/bin/hipcc $HIPFLAGS -fno-slp-vectorize $FLAGS -c $src -o $obj ;;
+        refit_kernel|lbvh_kernel) /opt/rocm/bin/hipcc $NOFTZ $FLAGS -c $src -o $obj ;;
+        *) /opt/rocm/bin/hipcc $HIPFLAGS $FLAGS -c $src -o $obj ;;
+    esac
+    OBJS="$OBJS $obj"
+done
+for src in $D/csrc/*.cpp; do   # mrt_api, tune, launch_plan, compat_api, wide_bvh, ... (whichever the revision has)
     obj=$B/$(basename $src .cpp).o
     /opt/rocm/bin/hipcc $HIPFLAGS $FLAGS -x hip -c $src -o $obj
     OBJS="$OBJS $obj"

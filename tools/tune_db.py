@@ -11,6 +11,16 @@ fixed rule again; a challenger replaces the rule only when its median is 3 % fas
 (csrc/tune.cpp kTuneMargin).
 
   python tools/tune_db.py [--workload W ...] [--rounds 5] [--launches 20] [--out PATH]
+
+--backfill sweeps the backfilled static grids instead (cfg.backfill, csrc/launch_plan.cpp), a
+dimension the in-library tuner does not explore and saved schedules reach by import only: for
+the static schedules, k in {1, 2, 3} rays per lane x a residency cap of {2, 3, 4, 5} workgroups
+per CU x tail_lanes in {0, 8, 16} x {no modifier, each stage-2 modifier}, against the persistent
+static schedules under the same modifiers and against the schedule saved today. In a backfilled
+launch every wave "cannot refill" after its last round, so the frontier tail fires in every wave:
+tail_lanes is a first-class knob there. A winner replaces the saved schedule only when its median
+is --margin faster, re-timed interleaved with it; tail_lanes 8 is a tracer setting no saved code
+carries, so it is reported and never written.
 """
 import argparse
 import os
@@ -34,6 +44,105 @@ def variant_key(any_hit, exact, lds_stack=16, nodes=1, tail=False, secondary=Fal
             | (256 if tail else 0) | (512 if secondary else 0))
 
 
+STATIC_SCHEDULES = {0: 20, 5: 16, 6: 12, 1: 8}   # stage-1 schedule: its waves/CU (csrc/tune.cpp tune_candidate)
+BACKFILL_K, BACKFILL_CAPS, BACKFILL_TAILS = (1, 2, 3), (2, 3, 4, 5), (0, 8, 16)
+
+
+def backfill_code(code16, k, cap):
+    """mrt_tuned_schedule.candidate: the 16-bit code | k << 16 | cap << 24 (include/mrt.h)."""
+    return code16 | (k << 16) | (cap << 24)
+
+
+def code_name(c):
+    s = f"{c & 0xff}/{(c >> 8) & 0xff}"
+    return s + (f" k{(c >> 16) & 0xff} cap{c >> 24}" if c >> 16 else "")
+
+
+def sweep_backfill(args, wl, tracer, b, store, fingerprint, exact):
+    """The --backfill sweep of one workload; returns the candidate written, or None."""
+    import torch
+    import bench
+    from mrt import _lib
+    launches = [tracer.launcher(rb, exact_rcp=exact) for rb, _ in b.batches]
+    default_tail = tracer.config()["tail_lanes"]
+
+    def keys_now():
+        cfg = tracer.config()
+        tail = cfg["tail_lanes"] > 0 and cfg["wide"] == 1
+        return sorted({(rb.size, variant_key(not rb.need_closest_hit, exact, tail=tail, secondary=rb.secondary))
+                       for rb, _ in b.batches})
+
+    def timed(items):
+        """items: (tail_lanes, code); interleaved rounds, the median of each."""
+        t = {it: [] for it in items}
+        for r in range(args.rounds + 1):
+            tail_set = None
+            for it in items:
+                tail, code = it
+                if tail != tail_set:
+                    tracer.set_config(tail_lanes=tail)
+                    tail_set = tail
+                tracer.load_schedules([(n, v, code, _lib.MRT_TUNE_VERSION) for n, v in keys_now()])
+                for go in launches * 3:
+                    go()
+                a_, z_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a_.record()
+                for _ in range(args.launches):
+                    for go in launches:
+                        go()
+                z_.record()
+                torch.cuda.synchronize()
+                if r:
+                    t[it].append(a_.elapsed_time(z_) / args.launches)
+        return {it: float(np.median(v)) for it, v in t.items()}
+
+    try:
+        keys = keys_now()
+        saved = {(n, v): c for n, v, c, _ in store.entries(fingerprint)}
+        incumbent = (default_tail, saved.get(keys[0], 0))
+        mods = [None] + list(range(N_SCHEDULES, N_SCHEDULES + STAGE2))
+        items = [incumbent]
+        for tail in BACKFILL_TAILS:
+            for m in mods:
+                for sched in STATIC_SCHEDULES:
+                    items.append((tail, sched if m is None else m | (sched << 8)))
+                for k in BACKFILL_K:
+                    for cap in BACKFILL_CAPS:
+                        items.append((tail, backfill_code(1 if m is None else m | (1 << 8), k, cap)))
+        items = sorted(set(items))
+        s1 = timed(items)
+        print(f"{wl} exact={exact}: backfill sweep, ms per launch (tail_lanes, code = locked/schedule k cap); "
+              f"saved {code_name(incumbent[1])} {s1[incumbent]:.4f}")
+        for tail in BACKFILL_TAILS:
+            for k in (0,) + BACKFILL_K:
+                row = {it: v for it, v in s1.items() if it[0] == tail and ((it[1] >> 16) & 0xff) == k}
+                best = sorted(row, key=row.get)[:4]
+                print(f"  tail {tail:2d} k {k}: " + "  ".join(f"{code_name(c)}:{row[(t_, c)]:.4f}" for t_, c in best))
+        for m in mods:   # the k x cap grid of each modifier at the default tail
+            for k in BACKFILL_K:
+                print(f"  grid mod {m} k {k} tail {default_tail}: " + " ".join(
+                    f"cap{cap}:{s1[(default_tail, backfill_code(1 if m is None else m | (1 << 8), k, cap))]:.4f}"
+                    for cap in BACKFILL_CAPS))
+        # the two fastest of each kind against the saved schedule again, interleaved
+        filled = sorted((it for it in s1 if it[1] >> 16), key=s1.get)[:2]
+        resident = sorted((it for it in s1 if not it[1] >> 16), key=s1.get)[:2]
+        s2 = timed(sorted(set([incumbent] + filled + resident)))
+        print("  final: " + "  ".join(f"tail {t_} {code_name(c)}:{v:.4f}" for (t_, c), v in sorted(s2.items(), key=lambda kv: kv[1])))
+        writable = [it for it in s2 if it[0] == default_tail]   # a saved code carries no tail_lanes of its own
+        best = min(writable, key=s2.get)
+        if best != incumbent and s2[best] < (1 - args.margin) * s2[incumbent]:
+            tracer.set_config(tail_lanes=default_tail)
+            tracer.load_schedules([(n, v, best[1], _lib.MRT_TUNE_VERSION) for n, v in keys_now()])
+            store.update(fingerprint, tracer.schedules())
+            print(f"  -> {code_name(best[1])} ({bench.schedule_name(best[1] & 0xffff)}), "
+                  f"{100 * (s2[incumbent] / s2[best] - 1):.1f} % faster than the saved schedule: written", flush=True)
+            return best[1]
+        print(f"  -> the saved schedule stays (best {code_name(best[1])} is within {100 * args.margin:.0f} %)", flush=True)
+        return None
+    finally:
+        tracer.set_config(tail_lanes=default_tail)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", action="append")
@@ -46,6 +155,8 @@ def main():
                          "one BVH and batch size share a key in --out, the last tuned wins there")
     ap.add_argument("--margin", type=float, default=MARGIN,
                     help="how much faster (median) a candidate must be to replace the rule (the library's 3 %%)")
+    ap.add_argument("--backfill", action="store_true",
+                    help="sweep the backfilled static grids (k x residency cap x tail_lanes x modifiers) instead")
     args = ap.parse_args()
     import torch
     import bench
@@ -65,6 +176,11 @@ def main():
         e = scenes.get(bench.workload_spec(wl)[0])
         b = bench.Batches(wl, e["scene"], e["gbvh"], tracer)
         for exact in ([True, False] if args.fast_rcp else [True]):
+            if args.backfill:
+                chosen = sweep_backfill(args, wl, tracer, b, store, e["gbvh"].fingerprint, exact)
+                if chosen is not None:
+                    cells[f"{wl}{'' if exact else ':fast'}"] = {"fingerprint": e["gbvh"].fingerprint, "candidate": chosen}
+                continue
             launches = [tracer.launcher(rb, exact_rcp=exact) for rb, _ in b.batches]
             cfg = tracer.config()
             tail = cfg["tail_lanes"] > 0 and cfg["wide"] == 1   # the library's with_tail()
