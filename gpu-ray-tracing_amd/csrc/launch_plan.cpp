@@ -3,6 +3,8 @@
 
 #include <algorithm>
 
+#include "deal_common.hpp"
+
 namespace mrt {
 namespace {
 
@@ -22,6 +24,11 @@ int64_t backfill_blocks(int64_t numRays, int k, int blockThreads) {
     const int64_t lanes = (numRays + k - 1) / k;
     const int64_t blocks = (lanes + blockThreads - 1) / blockThreads;
     return (blocks + 7) / 8 * 8;
+}
+
+int64_t oneshot_blocks(int numRays, int dealBlockLog2, int blockThreads) {
+    const int c = deal::chunk(numRays, dealBlockLog2);
+    return (int64_t)deal::kGroups * deal::blocks_per_group(c, blockThreads);
 }
 
 int cap_dyn_lds(int blocks, int staticLds, int ldsPerCU) {
@@ -48,6 +55,26 @@ LaunchPlan plan_launch(const LaunchPlanIn& in) {
     p.dynLds = 0;
     p.spillInts = entries * resident * in.blockThreads;
     if (in.backfill <= 0 || in.numRays <= 0) return p;
+
+    // The one-shot grid: only when the batch does not fit the resident grid (then there is nothing
+    // to backfill) and the slab of its launched lanes fits the cap (else k > 1: not one-shot).
+    if (in.oneshot == 1 && in.backfill == 1 && (in.dealBlockLog2 == 0 || (in.dealBlockLog2 >= deal::kMinBlockLog2 &&
+                                                                          in.dealBlockLog2 <= deal::kMaxBlockLog2)) &&
+        backfill_blocks(in.numRays, 1, in.blockThreads) > resident) {
+        const int64_t blocks = oneshot_blocks(in.numRays, in.dealBlockLog2, in.blockThreads);
+        const int64_t spillInts = entries * blocks * in.blockThreads;
+        int dyn = 0;
+        if (perCU < in.occBlocks) dyn = cap_dyn_lds(perCU, in.staticLds, in.ldsPerCU);
+        if (spillInts * (int64_t)sizeof(int32_t) <= in.spillCapBytes && dyn >= 0 && blocks * in.blockThreads <= 0x7fffffffll) {
+            p.blocks = (int)blocks;
+            p.backfill = 1;
+            p.dynLds = dyn;
+            p.spillInts = spillInts;
+            p.oneshot = 1;
+            p.dealBlockLog2 = in.dealBlockLog2;
+            return p;
+        }
+    }
 
     // The smallest k from the asked one whose slab fits the cap: the slab is indexed by the
     // launched lane, so it grows with the grid, and a larger k is a smaller grid.

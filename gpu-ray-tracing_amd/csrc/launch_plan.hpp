@@ -13,6 +13,12 @@
 // the workgroup waited for may not be resident yet. The static strided rounds
 // (num_queues = -1) have no such wait, and the plan is made for them only (valid_cfg
 // refuses a backfill with queues or with the ray sort).
+//
+// A one-shot grid (cfg.oneshot, with backfill = 1) is the backfilled grid of the one-shot kernels:
+// every lane at most one ray, dealt by deal_common.hpp in chunks of c positions per XCD group, so
+// 8 * ceil(c / blockThreads) workgroups; with a block-cyclic deal c may exceed ceil(numRays / 8).
+// Where it cannot be had (the batch fits the resident grid, or its slab exceeds the cap and would
+// need more than one ray per lane) the plan is the one made without it, unchanged.
 #pragma once
 
 #include <cstdint>
@@ -35,6 +41,8 @@ struct LaunchPlanIn {
     int occBlocks = 1;       // workgroups per CU the code object admits without dynamic LDS
     int spillEntries = 0;    // stackCap - S: spill-slab ints per lane
     int64_t spillCapBytes = kSpillCapBytes;
+    int oneshot = 0;         // 1: plan the one-shot grid (backfill == 1; the figures are the one-shot kernel's)
+    int dealBlockLog2 = 0;   // its deal: 0 = contiguous chunks, 6..15 = 2^b-ray blocks dealt cyclically
 };
 
 struct LaunchPlan {
@@ -43,12 +51,16 @@ struct LaunchPlan {
     int blocksPerCU = 0;     // workgroups resident per CU
     int dynLds = 0;          // dynamic LDS bytes per workgroup (the residency cap); 0: none needed
     int64_t spillInts = 0;   // spillEntries * launched lanes
+    int oneshot = 0;         // 1: the one-shot grid was planned (else: the plan made without in.oneshot)
+    int dealBlockLog2 = 0;   // its deal (0 when not one-shot)
 };
 
 // Workgroups per CU of a launch asked for wavesPerCU waves on a code object admitting occBlocks.
 int plan_blocks_per_cu(int wavesPerCU, int occBlocks, int blockThreads = 256);
 // Workgroups of a grid whose lanes take at most k rays each, a multiple of 8 (one XCD group each).
 int64_t backfill_blocks(int64_t numRays, int k, int blockThreads = 256);
+// Workgroups of the one-shot grid that deals numRays in 2^b-ray blocks (b = 0: contiguous chunks).
+int64_t oneshot_blocks(int numRays, int dealBlockLog2, int blockThreads = 256);
 // Dynamic LDS bytes with which exactly `blocks` workgroups of staticLds static bytes fit a CU's
 // ldsPerCU; -1 when no size does (the static bytes alone admit fewer).
 int cap_dyn_lds(int blocks, int staticLds, int ldsPerCU);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/mrt.h"
+#include "deal_common.hpp"
 #include "lbvh_common.hpp"
 #include "launch_plan.hpp"
 #include "lbvh_kernel.hpp"
@@ -96,15 +97,15 @@ struct mrt_tracer {
     uint64_t useClock = 0;   // launches of this handle (the workspaces' LRU order; guarded by mu)
     hipEvent_t evStart = nullptr, evStop = nullptr;
 
-    // Occupancy per kernel variant (index variant_key(), below 256), queried once
+    // Occupancy per kernel (index kernel_key(), below 1024), queried once
     // (hipOccupancy* is a host round-trip that would otherwise sit on every launch).
-    int occ[512] = {};
+    int occ[1024] = {};
     // Backfilled launches (launch_plan.hpp): per variant and residency cap of 1..kMaxCapBlocks
     // workgroups per CU, the dynamic LDS bytes + 1 that the occupancy query confirmed to give
     // exactly that residency (0: not asked yet, -1: none found, such launches run persistent).
     static constexpr int kMaxCapBlocks = 8;
-    int capDyn[512][kMaxCapBlocks + 1] = {};
-    int staticLds[512] = {};   // per variant: the kernel's static LDS bytes + 1 (0: not asked yet)
+    int capDyn[1024][kMaxCapBlocks + 1] = {};
+    int staticLds[1024] = {};   // per kernel: its static LDS bytes + 1 (0: not asked yet)
 
     // cfg.autotune: per (batch size, variant) the ray-distribution schedule the
     // measured launches chose (tune.cpp), reset on bind/set_config.
@@ -207,6 +208,8 @@ mrt_launch_cfg default_cfg() {
     c.ray_sort = 0;
     c.queue_xcc_mask = 0;
     c.backfill = 0;          // the persistent grid
+    c.oneshot = 0;           // the persistent kernels
+    c.deal_block = 0;
     return c;
 }
 
@@ -224,7 +227,12 @@ bool valid_cfg(const mrt_launch_cfg& c) {
            c.backfill >= 0 && c.backfill <= mrt::kMaxBackfill &&
            // a backfilled grid is oversubscribed: only the static rounds, in which no workgroup waits for
            // another (the queues' unserved-queue sweep does), and not the one-round ray sort
-           (c.backfill == 0 || (c.num_queues < 0 && c.ray_sort == 0));
+           (c.backfill == 0 || (c.num_queues < 0 && c.ray_sort == 0)) &&
+           // the one-shot kernels serve a grid of one ray per lane only (no queues and no ray sort: the
+           // line above), and the deal's blocks are theirs
+           (c.oneshot == 0 || (c.oneshot == 1 && c.backfill == 1)) &&
+           (c.deal_block == 0 ||
+            (c.oneshot == 1 && c.deal_block >= mrt::deal::kMinBlockLog2 && c.deal_block <= mrt::deal::kMaxBlockLog2));
 }
 
 // The frontier tail runs in the exact 4-wide kernels whose leaf refs carry counts.
@@ -256,18 +264,25 @@ mrt::TraceVariant variant_for(const mrt_tracer* t, uint32_t flags) {
 constexpr int kAutoRaysPerLane = 12;
 constexpr int kAutoMinWaves = 8;
 
-// The key of a kernel variant: its slot in mrt_tracer::occ, and its part of the tuning key.
+// The key of a kernel variant: its part of the tuning key (a saved schedule's one-shot bits are
+// part of the schedule, not of the key).
 int variant_key(const mrt::TraceVariant& v) {
     const int lds = v.ldsStack == 8 ? 0 : v.ldsStack == 16 ? 1 : 2;
-    static_assert((15 | (2 << 4) | (mrt::kNodeWide4Q << 6) | (1 << 8)) < (int)(sizeof(mrt_tracer::occ) / sizeof(int)),
-                  "every variant_key indexes mrt_tracer::occ");
     return (v.anyHit ? 1 : 0) | (v.speculative ? 2 : 0) | (v.exactRcp ? 4 : 0) | (v.stats ? 8 : 0) | (lds << 4) |
-           (v.nodes << 6) | (v.tail ? 256 : 0);   // < 512 = the size of mrt_tracer::occ
+           (v.nodes << 6) | (v.tail ? 256 : 0);   // < 512
+}
+
+// The key of a kernel function: its slot in mrt_tracer::occ, capDyn and staticLds (a variant's
+// one-shot sibling is a function of its own: other registers, less static LDS).
+int kernel_key(const mrt::TraceVariant& v) {
+    static_assert((15 | (2 << 4) | (mrt::kNodeWide4Q << 6) | (1 << 8) | (1 << 9)) < (int)(sizeof(mrt_tracer::occ) / sizeof(int)),
+                  "every kernel_key indexes mrt_tracer::occ");
+    return variant_key(v) | (v.oneshot ? 512 : 0);
 }
 
 // Workgroups per CU the code object of a variant admits (queried once).
 int variant_occupancy(mrt_tracer* t, const mrt::TraceVariant& v) {
-    int& occ = t->occ[variant_key(v)];
+    int& occ = t->occ[kernel_key(v)];
     if (occ <= 0 && (mrt::trace_occupancy(v, &occ) != hipSuccess || occ <= 0)) occ = 1;
     return occ;
 }
@@ -294,6 +309,9 @@ int grid_waves_per_cu(const mrt_tracer* t, const mrt_launch_cfg& cfg, int numRay
 }
 
 static_assert(mrt::kTuneMaxBackfill == mrt::kMaxBackfill, "tune.hpp restates launch_plan.hpp's kMaxBackfill");
+static_assert(mrt::TuneState::kTuneMinDealBlock == mrt::deal::kMinBlockLog2 &&
+                  mrt::TuneState::kTuneMaxDealBlock == mrt::deal::kMaxBlockLog2,
+              "tune.hpp restates deal_common.hpp's block range");
 
 // The dynamic LDS with which exactly perCU workgroups of variant v are resident per CU, confirmed
 // by the occupancy query once per (variant, perCU); -1 when no size is confirmed. The arithmetic
@@ -301,7 +319,7 @@ static_assert(mrt::kTuneMaxBackfill == mrt::kMaxBackfill, "tune.hpp restates lau
 // a launch never runs at a residency nobody confirmed.
 int confirmed_cap_lds(mrt_tracer* t, const mrt::TraceVariant& v, int perCU, int staticLds, int proposed) {
     if (perCU < 1 || perCU > mrt_tracer::kMaxCapBlocks) return -1;
-    int& slot = t->capDyn[variant_key(v)][perCU];
+    int& slot = t->capDyn[kernel_key(v)][perCU];
     if (slot != 0) return slot > 0 ? slot - 1 : -1;
     slot = -1;
     constexpr int kStep = 1024, kMaxSteps = 32;
@@ -335,13 +353,15 @@ mrt::LaunchPlan launch_plan(mrt_tracer* t, const mrt_launch_cfg& cfg, const mrt:
     in.ldsPerCU = t->ldsPerCU;
     mrt::LaunchPlan persistent = mrt::plan_launch(in);
     if (cfg.backfill <= 0 || cfg.num_queues >= 1 || t->ldsPerCU <= 0) return persistent;
-    int& lds = t->staticLds[variant_key(v)];
+    int& lds = t->staticLds[kernel_key(v)];
     if (lds == 0) {   // from the function's attributes, once per variant (a host round trip)
         hipFuncAttributes attr{};
         if (mrt::trace_kernel_attributes(v, &attr) != hipSuccess) return persistent;
         lds = (int)attr.sharedSizeBytes + 1;
     }
     in.backfill = cfg.backfill;
+    in.oneshot = v.oneshot ? 1 : 0;   // the plan of the one-shot kernel, from its own occupancy and static LDS
+    in.dealBlockLog2 = cfg.deal_block;
     in.staticLds = lds - 1;
     mrt::LaunchPlan p = mrt::plan_launch(in);
     if (p.backfill > 0 && p.dynLds > 0) {
@@ -609,6 +629,7 @@ mrt::TraceArgs trace_args(const mrt_tracer* t, const mrt_launch_cfg& cfg, const 
     a.stackBound = wide ? t->wideStackBound : stackCap - 1;
     a.tailLanes = cfg.tail_lanes;
     a.xccMask = cfg.queue_xcc_mask;
+    a.dealBlockLog2 = v.oneshot ? cfg.deal_block : 0;
     a.raySort = cfg.ray_sort;
     a.queues = ws->queues;
     a.spill = ws->spill;
@@ -686,7 +707,14 @@ int trace_impl(mrt_tracer* t, const void* rays, void* results, int32_t numRays, 
     }
     v.tail = with_tail(t, v, cfg);   // a tuned candidate may run without the tail
     const int stackCap = v.nodes != mrt::kNodeCompact2 ? t->wideStackCap : mrt::kStackCapacity;
-    const mrt::LaunchPlan plan = launch_plan(t, cfg, v, numRays, stackCap);
+    // cfg.oneshot: the one-shot sibling on the grid planned for it; where the variant has none, the batch
+    // fits the resident grid or the slab cap asks for more than one ray per lane, today's kernel and plan
+    v.oneshot = cfg.oneshot == 1 && cfg.backfill == 1 && mrt::trace_has_oneshot(v);
+    mrt::LaunchPlan plan = launch_plan(t, cfg, v, numRays, stackCap);
+    if (v.oneshot && !plan.oneshot) {
+        v.oneshot = false;
+        plan = launch_plan(t, cfg, v, numRays, stackCap);
+    }
     const int blocks = plan.blocks;
     const int totalLanes = blocks * mrt::kBlockThreads;
     mrt::Workspace* ws = nullptr;
@@ -704,6 +732,8 @@ int trace_impl(mrt_tracer* t, const void* rays, void* results, int32_t numRays, 
     info->autotune_candidate = tune ? tune->info_code(cand) : -1;
     info->autotune_locked = tune && tune->locked >= 0 ? 1 : 0;
     info->backfill = plan.backfill;
+    info->oneshot = plan.oneshot;
+    info->deal_block = plan.oneshot ? plan.dealBlockLog2 : 0;
     info->blocks_per_cu = plan.blocksPerCU;
     info->dyn_lds_bytes = plan.dynLds;
     return fill_info(t, v, a, ws, info);
@@ -1094,6 +1124,8 @@ int mrt_tracer_set_config(mrt_tracer* t, const mrt_launch_cfg* cfg) {
     if (c.queue_xcc_mask < 0) c.queue_xcc_mask = d.queue_xcc_mask;
     if (c.ray_sort < 0) c.ray_sort = d.ray_sort;
     if (c.backfill < 0) c.backfill = d.backfill;
+    if (c.oneshot < 0) c.oneshot = d.oneshot;
+    if (c.deal_block < 0) c.deal_block = d.deal_block;
     if (!valid_cfg(c)) return fail(MRT_ERR_INVALID_ARG, "launch config out of range");
     std::lock_guard<std::mutex> lock(t->mu);
     t->cfg = c;

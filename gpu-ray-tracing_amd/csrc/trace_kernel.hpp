@@ -59,6 +59,9 @@ struct TraceArgs {
                                // to its waves by direction octant (exact 4-wide kernels)
     int xccMask;               // test hook (cfg.queue_xcc_mask): > 0 = a wave's queue is (XCC_ID & mask) %
                                // numQueues, so the queues above mask have no waves of their own
+    int dealBlockLog2;         // one-shot kernels (cfg.oneshot): 0 = each XCD group traces one contiguous chunk,
+                               // b = 2^b-ray blocks dealt cyclically over the groups (deal_common.hpp); in what
+                               // was the padding before `queues`, so no other field moves
     unsigned* queues;          // numQueues heads, kQueueStrideWords apart, zeroed per launch
     int* spill;                // (stackCap - S) * totalLanes ints
     int* status;               // [0] = stack overflow count (entries pushed past stackCap)
@@ -78,6 +81,7 @@ struct TraceVariant {
     int ldsStack;       // 8, 16 or 32 LDS entries per lane
     int nodes = 0;      // kNodeCompact2, or a 4-wide form derived from it (speculative mode only)
     bool tail = false;  // kNodeWide4 with leaf counts: the instantiation with the frontier tail
+    bool oneshot = false;   // the one-shot sibling (every lane at most one ray; trace_has_oneshot)
 };
 
 // The 4-wide node array derived from a Compact2 node array (numNodes inner nodes,
@@ -102,6 +106,9 @@ int64_t wide_stack_bound(const uint32_t* wide, int64_t numWide, int nodeWords);
 // output) when some child box has no finite quantization (non-finite planes).
 bool build_wide4q(const int32_t* nodes, int64_t numNodes, std::vector<uint32_t>* out, const int32_t* woopX = nullptr,
                   int64_t woopSlots = 0);
+
+// Whether a variant has a one-shot sibling (launching one that has none is hipErrorInvalidValue).
+bool trace_has_oneshot(const TraceVariant& v);
 
 // Launch one trace. grid = number of 256-thread workgroups: all resident at once (the persistent
 // launch), or more (a backfilled static launch, launch_plan.hpp), then with dynLdsBytes of

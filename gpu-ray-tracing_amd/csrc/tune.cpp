@@ -93,6 +93,8 @@ mrt_launch_cfg tune_candidate(int numXccs, const mrt_launch_cfg& base, int c, co
         // cap, that many workgroups resident per CU
         x.backfill = st->backfill;
         if (st->capBlocks > 0) x.waves_per_cu = 4 * st->capBlocks;
+        x.oneshot = st->oneshot;
+        x.deal_block = st->dealBlock;
     }
     return x;
 }
@@ -197,7 +199,8 @@ int TuneState::info_code(int c) const {
 // candidate field: the locked candidate | the stage-1 winner << 8 (stage-2 candidates
 // are the stage-1 schedule with another speculation slack)
 int TuneState::export_code() const {
-    return locked | (std::max(0, stage1) << 8) | (backfill << kBackfillShift) | (capBlocks << kCapShift);
+    return locked | (std::max(0, stage1) << 8) | (backfill << kBackfillShift) | (capBlocks << kCapShift) |
+           (oneshot << kOneshotShift) | (dealBlock << kDealShift);
 }
 
 int TuneState::pick(int incumbent, int first, int last) const {
@@ -283,7 +286,7 @@ int TuneState::next_launch(int* slot) {
 TuneState* TuneTable::lookup(const mrt_launch_cfg& uc, const mrt_launch_cfg& rule, uint32_t flags, int numRays,
                              int variant, const void* stream) {
     if (!(uc.autotune && uc.num_queues < 0 && uc.waves_per_cu == 0 && uc.fetch_threshold == 0 && uc.lane_groups == 1 &&
-          uc.backfill == 0 && !(flags & MRT_TRACE_STATS)))
+          uc.backfill == 0 && uc.oneshot == 0 && uc.deal_block == 0 && !(flags & MRT_TRACE_STATS)))
         return nullptr;
     // secondary rays (MRT_TRACE_SECONDARY) settle their own schedule: a diffuse batch of a primary
     // batch's size runs differently (round-5 README table: Mori primary 4829 Mrays/s on the diffuse
@@ -316,6 +319,8 @@ TuneState* TuneTable::lookup(const mrt_launch_cfg& uc, const mrt_launch_cfg& rul
             tune->locked = kv.second->locked;
             tune->backfill = kv.second->backfill;
             tune->capBlocks = kv.second->capBlocks;
+            tune->oneshot = kv.second->oneshot;
+            tune->dealBlock = kv.second->dealBlock;
             tune->inherited = true;
         }
         tunes[key] = tune;
@@ -347,9 +352,14 @@ int TuneTable::import_schedules(const mrt_tuned_schedule* in, int count) {
         const int code = in[i].candidate;
         if (code < 0 || (code >> TuneState::kCodeBits) != 0) return MRT_ERR_INVALID_ARG;
         const int locked = code & 0xff, stage1 = (code >> 8) & 0xff;
-        const int backfill = (code >> TuneState::kBackfillShift) & 0xff, cap = (code >> TuneState::kCapShift) & 7;
+        const int backfill = (code >> TuneState::kBackfillShift) & 0x7f, cap = (code >> TuneState::kCapShift) & 7;
+        const int oneshot = (code >> TuneState::kOneshotShift) & 1, deal = (code >> TuneState::kDealShift) & 15;
         if (in[i].version != MRT_TUNE_VERSION || in[i].num_rays <= 0 || locked >= TuneState::kSchedules + TuneState::kStage2 ||
             stage1 >= TuneState::kSchedules || backfill > kTuneMaxBackfill || (cap > 0 && backfill == 0))
+            return MRT_ERR_INVALID_ARG;
+        // one-shot is a grid of one ray per lane; the deal's blocks are the one-shot kernels'
+        if ((oneshot && backfill != 1) || (deal != 0 && (!oneshot || deal < TuneState::kTuneMinDealBlock ||
+                                                          deal > TuneState::kTuneMaxDealBlock)))
             return MRT_ERR_INVALID_ARG;
         // a backfilled grid is for the static schedules only: no workgroup of theirs waits for another
         const int sched = locked < TuneState::kSchedules ? locked : stage1;
@@ -364,8 +374,10 @@ int TuneTable::import_schedules(const mrt_tuned_schedule* in, int count) {
         }
         it->second->stage1 = (in[i].candidate >> 8) & 0xff;
         it->second->locked = in[i].candidate & 0xff;
-        it->second->backfill = (in[i].candidate >> TuneState::kBackfillShift) & 0xff;
+        it->second->backfill = (in[i].candidate >> TuneState::kBackfillShift) & 0x7f;
         it->second->capBlocks = (in[i].candidate >> TuneState::kCapShift) & 7;
+        it->second->oneshot = (in[i].candidate >> TuneState::kOneshotShift) & 1;
+        it->second->dealBlock = (in[i].candidate >> TuneState::kDealShift) & 15;
         it->second->inherited = false;   // a schedule saved for this very key: exported again
     }
     return MRT_OK;

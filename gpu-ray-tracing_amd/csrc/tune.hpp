@@ -83,6 +83,10 @@ struct TuneState {
     // residency cap in workgroups per CU (0: the schedule's own waves/CU). Static schedules only.
     int backfill = 0;
     int capBlocks = 0;
+    // and its one-shot kernel (cfg.oneshot, only with backfill 1) with its deal (cfg.deal_block):
+    // by import only, like the backfill
+    int oneshot = 0;
+    int dealBlock = 0;
     const void* stream = nullptr;    // the stream this batch size was first launched on (only compared)
     bool multiStream = false;        // launched on several streams: not explored (settled schedule or the rule)
     bool inherited = false;          // took a nearby batch size's schedule (kTuneInherit): not exported
@@ -105,8 +109,11 @@ struct TuneState {
     int info_code(int c) const;
     int export_code() const;
     // mrt_tuned_schedule.candidate: the locked candidate (bits 0-7), the schedule it modifies (8-15),
-    // the backfill k (16-23, at most kTuneMaxBackfill) and the residency cap (24-26); the rest zero.
-    static constexpr int kBackfillShift = 16, kCapShift = 24, kCodeBits = 27;
+    // the backfill k (16-22, at most kTuneMaxBackfill), one-shot (23), the residency cap (24-26) and the
+    // one-shot deal's block log2 (27-30: 0 or 6..15); bit 31 zero. A code from before the one-shot
+    // bits has them zero and means what it meant.
+    static constexpr int kBackfillShift = 16, kOneshotShift = 23, kCapShift = 24, kDealShift = 27, kCodeBits = 31;
+    static constexpr int kTuneMinDealBlock = 6, kTuneMaxDealBlock = 15;   // deal_common.hpp (mrt_api.cpp asserts it)
 
 private:
     int pick(int incumbent, int first, int last) const;

@@ -165,6 +165,23 @@ typedef struct mrt_launch_cfg {
                                   reports what a launch used. Refused with num_queues >= 1 and with
                                   ray_sort = 1 (MRT_ERR_INVALID_ARG); a tracer with it set is not autotuned.
                                   Results are unchanged: every ray is traced once either way           */
+    int32_t oneshot;           /* 1 = a backfilled grid of one ray per lane (backfill = 1) runs the one-shot
+                                  kernels: the lane's ray is computed once, in closed form, and the kernel
+                                  holds no refill loop, queue code or ray sort (fewer registers, no
+                                  spills). The exact 4-wide speculative traversal at lds_stack 16 has them;
+                                  another variant, a batch that fits the resident grid and one whose spill
+                                  slab asks for more than one ray per lane run the launch as without it
+                                  (mrt_trace_info.oneshot reports which). The grid is 8 * ceil(c / 256)
+                                  workgroups for c positions per XCD group (deal_block). 0 = off (default;
+                                  -1 = default). Refused unless backfill = 1 (so also with queues and
+                                  with ray_sort). Results are unchanged: every ray is traced once        */
+    int32_t deal_block;        /* oneshot = 1: 0 = each XCD group (blockIdx % 8) traces one contiguous chunk
+                                  of roundup64(ceil(numRays / 8)) rays, as the strided rounds deal them
+                                  (default; -1 = default). b = 6..15: the batch's 2^b-ray blocks are dealt
+                                  cyclically, block i to group i mod 8, so every XCD samples the whole
+                                  Morton-ordered frame and the groups cost alike; c = ceil(ceil(numRays /
+                                  2^b) / 8) * 2^b, which may exceed ceil(numRays / 8) (lanes past the batch
+                                  trace nothing). Refused without oneshot = 1 and outside {0, 6..15}     */
 } mrt_launch_cfg;
 
 /* Per-launch statistics reported back to the host (optional). */
@@ -196,6 +213,11 @@ typedef struct mrt_trace_info {
     int32_t blocks_per_cu;     /* workgroups resident per CU at once                                  */
     int32_t dyn_lds_bytes;     /* dynamic LDS per workgroup that caps the residency of a backfilled
                                   launch (0 = none needed, and in every persistent launch)            */
+    int32_t oneshot;           /* 1 = the launch ran the one-shot kernel on its own grid (cfg.oneshot or a
+                                  saved schedule's); 0 in every other launch, also where cfg.oneshot fell
+                                  back (see mrt_launch_cfg.oneshot)                                     */
+    int32_t deal_block;        /* log2 of the one-shot launch's deal blocks (0 = contiguous, and whenever
+                                  oneshot is 0)                                                       */
 } mrt_trace_info;
 
 /* What the last bind derived (mrt_tracer_bind_info). */
@@ -218,9 +240,11 @@ typedef struct mrt_tuned_schedule {
     int32_t num_rays;
     int32_t variant;
     int32_t candidate;         /* bits 0-15: the autotuner's code (mrt_trace_info.autotune_candidate);
-                                  bits 16-23: cfg.backfill of the schedule (static schedules only, 0..64);
+                                  bits 16-22: cfg.backfill of the schedule (static schedules only, 0..64);
+                                  bit 23: cfg.oneshot (only with a backfill of 1);
                                   bits 24-26: its residency cap in workgroups per CU (0 = the schedule's
-                                  own waves_per_cu); the bits above are zero                       */
+                                  own waves_per_cu); bits 27-30: cfg.deal_block (0 or 6..15, only with
+                                  bit 23); bit 31 is zero                                          */
     int32_t version;          /* MRT_TUNE_VERSION when exported; others are refused on import */
 } mrt_tuned_schedule;
 enum { MRT_TUNE_VERSION = 11 };   /* 11: round 6 (schedules re-tuned on the round-6 library) */

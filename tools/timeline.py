@@ -57,6 +57,15 @@ def main():
     print("  last-finishing waves (end us, rays, first starts):")
     for w, v in sorted(wend.items(), key=lambda kv: -kv[1][0])[:10]:
         print(f"    wave {w}: end {v[0]:.1f} rays {v[1]} starts {v[2]}")
+    # per XCD group (blockIdx % 8; four waves per workgroup): when the group's rays end. Groups that cost
+    # alike end together; under a contiguous deal of one round each group traces one eighth of the frame
+    grp = (wave // 4) % 8
+    print("  XCD group (blockIdx % 8): rays, steps (sum), 50 % / 99 % / last ray done (us):")
+    for g in range(8):
+        sel = grp == g
+        if sel.any():
+            print(f"    group {g}: {sel.sum():7d} rays {steps[sel].sum():10d} steps  {np.percentile(end[sel], 50):6.1f} "
+                  f"{np.percentile(end[sel], 99):6.1f} {end[sel].max():6.1f}")
     bins = np.linspace(0, end.max(), 41)
     inflight = [(int(((start <= t) & (end > t)).sum())) for t in bins]
     waves_live = [len(np.unique(wave[(start <= t) & (end > t)])) for t in bins]

@@ -21,6 +21,13 @@ launch every wave "cannot refill" after its last round, so the frontier tail fir
 tail_lanes is a first-class knob there. A winner replaces the saved schedule only when its median
 is --margin faster, re-timed interleaved with it; tail_lanes 8 is a tracer setting no saved code
 carries, so it is reported and never written.
+
+The same sweep covers the one-shot kernels (cfg.oneshot, cfg.deal_block; csrc/deal_common.hpp): every
+k = 1 grid at a cap of 4 and 5 workgroups per CU also runs with oneshot = 1 at deal_block 0 (the
+contiguous chunks: the same deal as today's kernel, so the difference is the kernel's code alone)
+and 10, 11, 12 (block-cyclic over the XCD groups: the deal alone, against deal_block 0). The final
+re-times, interleaved with the saved schedule, the best one-shot schedule, today's kernel on that
+same schedule, and the one-shot kernel on it at each deal.
 """
 import argparse
 import os
@@ -46,6 +53,8 @@ def variant_key(any_hit, exact, lds_stack=16, nodes=1, tail=False, secondary=Fal
 
 STATIC_SCHEDULES = {0: 20, 5: 16, 6: 12, 1: 8}   # stage-1 schedule: its waves/CU (csrc/tune.cpp tune_candidate)
 BACKFILL_K, BACKFILL_CAPS, BACKFILL_TAILS = (1, 2, 3), (2, 3, 4, 5), (0, 8, 16)
+ONESHOT_CAPS, ONESHOT_DEALS = (4, 5), (0, 10, 11, 12)
+ONESHOT_BIT, DEAL_SHIFT = 1 << 23, 27
 
 
 def backfill_code(code16, k, cap):
@@ -53,9 +62,19 @@ def backfill_code(code16, k, cap):
     return code16 | (k << 16) | (cap << 24)
 
 
+def oneshot_code(code, deal):
+    """A k = 1 code with the one-shot bit (23) and the deal's block log2 (bits 27-30)."""
+    return code | ONESHOT_BIT | (deal << DEAL_SHIFT)
+
+
+def is_oneshot(c):
+    return bool(c & ONESHOT_BIT)
+
+
 def code_name(c):
     s = f"{c & 0xff}/{(c >> 8) & 0xff}"
-    return s + (f" k{(c >> 16) & 0xff} cap{c >> 24}" if c >> 16 else "")
+    s += f" k{(c >> 16) & 0x7f} cap{(c >> 24) & 7}" if c >> 16 else ""
+    return s + (f" oneshot b{(c >> DEAL_SHIFT) & 15}" if is_oneshot(c) else "")
 
 
 def sweep_backfill(args, wl, tracer, b, store, fingerprint, exact):
@@ -108,26 +127,50 @@ def sweep_backfill(args, wl, tracer, b, store, fingerprint, exact):
                     items.append((tail, sched if m is None else m | (sched << 8)))
                 for k in BACKFILL_K:
                     for cap in BACKFILL_CAPS:
-                        items.append((tail, backfill_code(1 if m is None else m | (1 << 8), k, cap)))
+                        code = backfill_code(1 if m is None else m | (1 << 8), k, cap)
+                        items.append((tail, code))
+                        if k == 1 and cap in ONESHOT_CAPS:
+                            items += [(tail, oneshot_code(code, deal)) for deal in ONESHOT_DEALS]
         items = sorted(set(items))
         s1 = timed(items)
         print(f"{wl} exact={exact}: backfill sweep, ms per launch (tail_lanes, code = locked/schedule k cap); "
               f"saved {code_name(incumbent[1])} {s1[incumbent]:.4f}")
         for tail in BACKFILL_TAILS:
             for k in (0,) + BACKFILL_K:
-                row = {it: v for it, v in s1.items() if it[0] == tail and ((it[1] >> 16) & 0xff) == k}
+                row = {it: v for it, v in s1.items()
+                       if it[0] == tail and ((it[1] >> 16) & 0x7f) == k and not is_oneshot(it[1])}
                 best = sorted(row, key=row.get)[:4]
                 print(f"  tail {tail:2d} k {k}: " + "  ".join(f"{code_name(c)}:{row[(t_, c)]:.4f}" for t_, c in best))
+            for deal in ONESHOT_DEALS:
+                row = {it: v for it, v in s1.items()
+                       if it[0] == tail and is_oneshot(it[1]) and (it[1] >> DEAL_SHIFT) & 15 == deal}
+                best = sorted(row, key=row.get)[:4]
+                print(f"  tail {tail:2d} oneshot b{deal}: " + "  ".join(f"{code_name(c)}:{row[(t_, c)]:.4f}" for t_, c in best))
         for m in mods:   # the k x cap grid of each modifier at the default tail
             for k in BACKFILL_K:
                 print(f"  grid mod {m} k {k} tail {default_tail}: " + " ".join(
                     f"cap{cap}:{s1[(default_tail, backfill_code(1 if m is None else m | (1 << 8), k, cap))]:.4f}"
                     for cap in BACKFILL_CAPS))
         # the two fastest of each kind against the saved schedule again, interleaved
-        filled = sorted((it for it in s1 if it[1] >> 16), key=s1.get)[:2]
+        filled = sorted((it for it in s1 if it[1] >> 16 and not is_oneshot(it[1])), key=s1.get)[:2]
         resident = sorted((it for it in s1 if not it[1] >> 16), key=s1.get)[:2]
-        s2 = timed(sorted(set([incumbent] + filled + resident)))
+        # the best one-shot schedule at the default tail (a saved code carries no tail of its own), today's
+        # kernel on that schedule, and the one-shot kernel on it at every deal: deal 0 against today's
+        # kernel is the code generation alone, the cyclic deals against deal 0 the deal alone
+        shots = sorted((it for it in s1 if is_oneshot(it[1]) and it[0] == default_tail), key=s1.get)[:1]
+        family = []
+        for t_, c in shots:
+            plain = c & ~(ONESHOT_BIT | (15 << DEAL_SHIFT))
+            family += [(t_, plain)] + [(t_, oneshot_code(plain, deal)) for deal in ONESHOT_DEALS]
+        s2 = timed(sorted(set([incumbent] + filled + resident + shots + family)))
         print("  final: " + "  ".join(f"tail {t_} {code_name(c)}:{v:.4f}" for (t_, c), v in sorted(s2.items(), key=lambda kv: kv[1])))
+        for t_, c in shots:
+            plain = c & ~(ONESHOT_BIT | (15 << DEAL_SHIFT))
+            base, shot0 = s2[(t_, plain)], s2[(t_, oneshot_code(plain, 0))]
+            print(f"  one-shot on {code_name(plain)}: today's kernel {base:.4f}, one-shot b0 {shot0:.4f} "
+                  f"({100 * (base / shot0 - 1):+.1f} % code generation); " + "  ".join(
+                      f"b{d} {s2[(t_, oneshot_code(plain, d))]:.4f} ({100 * (shot0 / s2[(t_, oneshot_code(plain, d))] - 1):+.1f} % deal)"
+                      for d in ONESHOT_DEALS[1:]))
         writable = [it for it in s2 if it[0] == default_tail]   # a saved code carries no tail_lanes of its own
         best = min(writable, key=s2.get)
         if best != incumbent and s2[best] < (1 - args.margin) * s2[incumbent]:
