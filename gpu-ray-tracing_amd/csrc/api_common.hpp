@@ -1,0 +1,92 @@
+// api_common.hpp — what the C-ABI files (mrt_api.cpp, bind_api.cpp, refit_api.cpp, build_api.cpp,
+// compat_api.cpp) share: the error returns, the device guard, and the owners of the device
+// memory and the events the library allocates.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <utility>
+
+#include "../../include/mrt.h"
+#include "trace_kernel.hpp"   // api_fail
+
+namespace mrt {
+
+inline int fail(int code, const std::string& what) { return api_fail(code, what); }
+
+inline int hipFail(hipError_t e, const char* what) {
+    return fail(MRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define MRT_HIP(call)                                         \
+    do {                                                      \
+        hipError_t e_ = (call);                               \
+        if (e_ != hipSuccess) return ::mrt::hipFail(e_, #call); \
+    } while (0)
+
+// Restores the caller's current device on scope exit.
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// A hipMalloc'ed array of T, freed with its owner (a destructor has nobody to report to: the
+// error is dropped). Move-only; a moved-from or default-constructed one holds nothing.
+template <class T>
+struct DeviceBuf {
+    T* p = nullptr;
+    DeviceBuf() = default;
+    DeviceBuf(DeviceBuf&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+    DeviceBuf& operator=(DeviceBuf&& o) noexcept {
+        if (this != &o) {
+            (void)free();
+            p = std::exchange(o.p, nullptr);
+        }
+        return *this;
+    }
+    ~DeviceBuf() { (void)free(); }
+    // `bytes` of new memory in place of what it held; holds nothing when that fails.
+    hipError_t alloc(size_t bytes) {
+        (void)free();
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    hipError_t free() { return p ? hipFree(std::exchange(p, nullptr)) : hipSuccess; }
+    T* get() const { return p; }
+    explicit operator bool() const { return p != nullptr; }
+};
+
+// A hipEvent_t, destroyed with its owner. Move-only.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(std::exchange(o.e, nullptr)) {}
+    Event& operator=(Event&& o) noexcept {
+        if (this != &o) {
+            reset();
+            e = std::exchange(o.e, nullptr);
+        }
+        return *this;
+    }
+    ~Event() { reset(); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+    void reset() {
+        if (e) (void)hipEventDestroy(std::exchange(e, nullptr));
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+// The events around a timed launch.
+struct EventPair {
+    Event start, stop;
+};
+
+}  // namespace mrt

@@ -1,24 +1,18 @@
 // compat_api.cpp — the implicit per-device tracers (mrt_bind_bvh / mrt_unbind_bvh /
 // mrt_trace) and the reference-compatible entry points of CudaTracerKernels.hh:42-52,
 // written against the public mrt_* functions of include/mrt.h only.
-#include <hip/hip_runtime.h>
 #include <climits>
 
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
-#include <string>
 
-#include "../../include/mrt.h"
-#include "trace_kernel.hpp"
+#include "api_common.hpp"
+
+using mrt::fail;
+using mrt::hipFail;
 
 namespace {
-
-int fail(int code, const std::string& what) { return mrt::api_fail(code, what); }
-
-int hipFail(hipError_t e, const char* what) {
-    return fail(MRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 // ---- implicit per-device tracers (convenience + reference-compat API) ----
 constexpr int kMaxDevices = 64;

@@ -4,6 +4,8 @@
 #include <algorithm>
 
 #include "deal_common.hpp"
+#include "trace_limits.hpp"
+#include "tune.hpp"
 
 namespace mrt {
 namespace {
@@ -12,7 +14,109 @@ namespace {
 // a size is rounded (used where such a multiple lies inside the admissible range).
 constexpr int kLdsRound = 2048;
 
+// The production (speculative) traversal reads 4-wide nodes derived at bind time
+// (profiles/round2_tuning.md, "4-wide nodes").
+constexpr int kDefaultWide = 1;
+// Launch schedules are tuned per batch size (tune.cpp): equal or faster on
+// every workload once settled (+9...+16 % on bunny/dragon primary batches).
+constexpr int kDefaultAutotune = 1;
+
+// Rays per lane the automatic grid aims for: a frame-sized batch is bound by
+// its slowest rays, whose step latency grows with the number of co-resident
+// waves, so small batches get fewer waves per CU; big batches fill the CU.
+// Measured on MI355X (tools/sweep.py, profiles/round1_sweep.txt): batches that
+// fit one ray per lane at 32 waves/CU run fastest fully static (conference AO
+// 640x480: 0.061 ms vs 0.077 at 8 waves); above that, 8 waves/CU is best up to
+// ~1M rays (bunny primary 1024x768), 16 at 3M, 32 at 12M rays.
+constexpr int kAutoRaysPerLane = 12;
+constexpr int kAutoMinWaves = 8;
+
 }  // namespace
+
+mrt_launch_cfg default_cfg() {
+    mrt_launch_cfg c{};
+    c.waves_per_cu = 0;   // auto: sized from the batch (grid_waves_per_cu)
+    c.fetch_threshold = 0;   // strided mode: a wave refills once all its lanes are done
+    c.num_queues = -1;       // static strided assignment (see trace_kernel.hip); 1..8 = atomic queues
+    c.lds_stack = 16;
+    c.lane_groups = 1;
+    c.wide = kDefaultWide;
+    c.spec_slack = kDefaultSpecSlack;   // tune.hpp, like the tail: the autotuner changes them only at their defaults
+    c.static_rounds = 1;
+    c.autotune = kDefaultAutotune;
+    c.tail_lanes = kDefaultTailLanes;
+    c.queue_shared = 0;
+    c.queue_block = 0;
+    c.ray_sort = 0;
+    c.queue_xcc_mask = 0;
+    c.backfill = 0;          // the persistent grid
+    c.oneshot = 0;           // the persistent kernels
+    c.deal_block = 0;
+    return c;
+}
+
+mrt_launch_cfg resolve_cfg(const mrt_launch_cfg& user) {
+    mrt_launch_cfg c = user;
+    const mrt_launch_cfg d = default_cfg();
+    if (c.waves_per_cu == 0) c.waves_per_cu = d.waves_per_cu;
+    if (c.num_queues == 0) c.num_queues = d.num_queues;
+    if (c.lds_stack == 0) c.lds_stack = d.lds_stack;
+    if (c.lane_groups == 0) c.lane_groups = d.lane_groups;
+    if (c.wide < 0) c.wide = d.wide;   // -1 = library default
+    if (c.spec_slack < 0) c.spec_slack = d.spec_slack;
+    if (c.static_rounds == 0) c.static_rounds = d.static_rounds;
+    if (c.autotune < 0) c.autotune = d.autotune;
+    if (c.tail_lanes < 0) c.tail_lanes = d.tail_lanes;
+    if (c.queue_shared < 0) c.queue_shared = d.queue_shared;
+    if (c.queue_block < 0) c.queue_block = d.queue_block;
+    if (c.queue_xcc_mask < 0) c.queue_xcc_mask = d.queue_xcc_mask;
+    if (c.ray_sort < 0) c.ray_sort = d.ray_sort;
+    if (c.backfill < 0) c.backfill = d.backfill;
+    if (c.oneshot < 0) c.oneshot = d.oneshot;
+    if (c.deal_block < 0) c.deal_block = d.deal_block;
+    return c;
+}
+
+bool valid_cfg(const mrt_launch_cfg& c) {
+    return (c.waves_per_cu == 0 || (c.waves_per_cu >= 4 && c.waves_per_cu <= 32)) && c.fetch_threshold >= 0 && c.fetch_threshold <= 64 &&
+           (c.num_queues == -1 || (c.num_queues >= 1 && c.num_queues <= kMaxQueues)) &&
+           (c.lds_stack == 8 || c.lds_stack == 16 || c.lds_stack == 32) &&
+           c.lane_groups >= 1 && c.lane_groups <= 64 && (c.lane_groups & (c.lane_groups - 1)) == 0 &&
+           (c.wide >= 0 && c.wide <= 2) && c.spec_slack >= 0 && c.spec_slack <= 63 &&
+           c.static_rounds >= 1 && c.static_rounds <= 64 && (c.autotune == 0 || c.autotune == 1) &&
+           c.tail_lanes >= 0 && c.tail_lanes <= 16 &&
+           c.queue_shared >= 0 && c.queue_shared <= 100 && c.queue_block >= 0 && c.queue_block <= (1 << 20) &&
+           (c.queue_block & (c.queue_block - 1)) == 0 && (c.queue_block == 0 || c.queue_block >= 64) &&
+           c.queue_xcc_mask >= 0 && c.queue_xcc_mask <= 15 && (c.ray_sort == 0 || c.ray_sort == 1) &&
+           c.backfill >= 0 && c.backfill <= kMaxBackfill &&
+           // a backfilled grid is oversubscribed: only the static rounds, in which no workgroup waits for
+           // another (the queues' unserved-queue sweep does), and not the one-round ray sort
+           (c.backfill == 0 || (c.num_queues < 0 && c.ray_sort == 0)) &&
+           // the one-shot kernels serve a grid of one ray per lane only (no queues and no ray sort: the
+           // line above), and the deal's blocks are theirs
+           (c.oneshot == 0 || (c.oneshot == 1 && c.backfill == 1)) &&
+           (c.deal_block == 0 ||
+            (c.oneshot == 1 && c.deal_block >= deal::kMinBlockLog2 && c.deal_block <= deal::kMaxBlockLog2));
+}
+
+int grid_waves_per_cu(int numCUs, const mrt_launch_cfg& cfg, int numRays) {
+    int waves = cfg.waves_per_cu;
+    if (waves == 0 && cfg.num_queues < 0) {
+        // Static strided assignment: kStridedWaves per CU (tune.hpp).
+        waves = kStridedWaves;
+    } else if (waves == 0) {
+        const long long cus = std::max(1, numCUs);
+        if ((long long)numRays <= 32LL * 64 * cus) {
+            // The whole batch fits the first (static, atomic-free) round at full
+            // occupancy: one ray per lane, no dynamic fetch at all.
+            waves = 32;
+        } else {
+            const long long lanesPerCU = (long long)numRays / kAutoRaysPerLane / cus;
+            waves = (int)std::min<long long>(32, std::max<long long>(kAutoMinWaves, (lanesPerCU + 63) / 64));
+        }
+    }
+    return waves;
+}
 
 int plan_blocks_per_cu(int wavesPerCU, int occBlocks, int blockThreads) {
     const int wavesPerBlock = std::max(1, blockThreads / 64);

@@ -1,6 +1,8 @@
-// launch_plan.hpp — the grid, the residency cap and the spill slab of a trace launch.
-// Plain C++ with no HIP in it (like tune.hpp): mrt_api.cpp feeds it the device's and the
-// kernel's figures, tests/cpp/launch_plan_driver.cpp runs it on the CPU.
+// launch_plan.hpp — the launch configuration (its defaults, the "library default" sentinels of
+// mrt_tracer_set_config, its valid ranges and combinations, the waves per CU a batch gets) and
+// the grid, the residency cap and the spill slab of a trace launch.
+// Plain C++ with no HIP in it (like tune.hpp): mrt_api.cpp feeds it the caller's configuration,
+// the device's and the kernel's figures, tests/cpp/launch_plan_driver.cpp runs it on the CPU.
 //
 // Two kinds of grid. The persistent one holds as many workgroups as are resident at once;
 // each takes numRays / gridLanes static rounds. The backfilled one (cfg.backfill = k) is
@@ -23,7 +25,20 @@
 
 #include <cstdint>
 
+#include "../../include/mrt.h"
+
 namespace mrt {
+
+// The configuration of a new tracer, and what a "library default" sentinel stands for.
+mrt_launch_cfg default_cfg();
+// The caller's configuration with every sentinel (0 for waves_per_cu, num_queues, lds_stack,
+// lane_groups and static_rounds, negative for the fields after them) replaced by its default.
+mrt_launch_cfg resolve_cfg(const mrt_launch_cfg& user);
+// Whether a resolved configuration is one mrt_tracer_set_config accepts.
+bool valid_cfg(const mrt_launch_cfg& c);
+// Waves per CU a launch of numRays asks for on numCUs CUs: the configuration's, or what the
+// batch size suggests.
+int grid_waves_per_cu(int numCUs, const mrt_launch_cfg& cfg, int numRays);
 
 constexpr int kMaxBackfill = 64;         // rays per lane a backfilled grid may be sized for
 // Most bytes of a backfilled launch's spill slab, per workspace: the slab holds

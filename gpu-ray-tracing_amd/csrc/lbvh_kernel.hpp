@@ -1,4 +1,4 @@
-// lbvh_kernel.hpp — launch interface between the C-ABI glue (mrt_api.cpp) and the
+// lbvh_kernel.hpp — launch interface between the C-ABI glue (build_api.cpp) and the
 // gfx950 kernels that build a linear BVH's topology into Compact2 buffers
 // (lbvh_kernel.hip). Boxes and Woop rows are the refit kernels' (refit_kernel.hpp).
 #pragma once

@@ -1,5 +1,5 @@
-// refit_kernel.hpp — launch interface between the C-ABI glue (mrt_api.cpp) and the
-// gfx950 refit kernels (refit_kernel.hip).
+// refit_kernel.hpp — launch interface between the C-ABI glue (refit_api.cpp: enqueue_refit, which
+// the device build of build_api.cpp runs too) and the gfx950 refit kernels (refit_kernel.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -1,10 +1,12 @@
-// trace_kernel.hpp — launch interface between the C-ABI glue (mrt_api.cpp)
-// and the gfx950 traversal kernels (trace_kernel.hip).
+// trace_kernel.hpp — launch interface between the C-ABI glue (the trace path of mrt_api.cpp,
+// the wide derivation of bind_api.cpp) and the gfx950 traversal kernels (trace_kernel.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
 #include <vector>
+
+#include "trace_limits.hpp"   // kMaxQueues
 
 namespace mrt {
 
@@ -16,7 +18,6 @@ constexpr int kEntrypointSentinel = 0x76543210;
 // kepler_dynamic_fetch.cu:47). The top kLdsStack entries live in LDS, the
 // rest spill to a per-lane slab in HBM.
 constexpr int kStackCapacity = 64;
-constexpr int kMaxQueues = 8;
 constexpr int kQueueStrideWords = 64;      // one 256-B line per queue head
 #ifndef MRT_BLOCK_THREADS
 #define MRT_BLOCK_THREADS 256
@@ -129,7 +130,8 @@ hipError_t trace_kernel_attributes(const TraceVariant& v, hipFuncAttributes* att
 // inputs); adds the number of mismatching bit patterns to *mismatchesDev.
 hipError_t selftest_exact_rcp(unsigned long long* mismatchesDev, hipStream_t s);
 
-// Thread-local error detail behind mrt_last_error_detail() (csrc/mrt_api.cpp).
+// Thread-local error detail behind mrt_last_error_detail() (csrc/mrt_api.cpp; the C-ABI files
+// reach it through api_common.hpp's fail / hipFail / MRT_HIP).
 int api_fail(int code, const std::string& what);
 const char* api_last_error();
 

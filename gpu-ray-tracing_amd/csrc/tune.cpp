@@ -139,7 +139,7 @@ mrt_launch_cfg explored_candidate(int numXccs, const mrt_launch_cfg& base, int c
                   // Infinity Cache (hairball 2 M rays: 0.630 -> 0.547 ms, fabric bytes 1.07 -> 0.74 GB at
                   // 4096-ray blocks, profiles/round4_queue_ab.txt; 8192: 1.4 % faster again and the
                   // strong-scaling shards' best, round4_order_sweep.txt)
-            x.num_queues = std::max(1, std::min(numXccs, kTuneMaxQueues));   // one per XCD, never more
+            x.num_queues = std::max(1, std::min(numXccs, kMaxQueues));   // one per XCD, never more
             x.queue_block = kXcdQueueBlock;
             x.queue_shared = kXcdQueueShared;
             x.fetch_threshold = kXcdQueueThreshold;
@@ -353,13 +353,13 @@ int TuneTable::import_schedules(const mrt_tuned_schedule* in, int count) {
         if (code < 0 || (code >> TuneState::kCodeBits) != 0) return MRT_ERR_INVALID_ARG;
         const int locked = code & 0xff, stage1 = (code >> 8) & 0xff;
         const int backfill = (code >> TuneState::kBackfillShift) & 0x7f, cap = (code >> TuneState::kCapShift) & 7;
-        const int oneshot = (code >> TuneState::kOneshotShift) & 1, deal = (code >> TuneState::kDealShift) & 15;
+        const int oneshot = (code >> TuneState::kOneshotShift) & 1, block = (code >> TuneState::kDealShift) & 15;
         if (in[i].version != MRT_TUNE_VERSION || in[i].num_rays <= 0 || locked >= TuneState::kSchedules + TuneState::kStage2 ||
-            stage1 >= TuneState::kSchedules || backfill > kTuneMaxBackfill || (cap > 0 && backfill == 0))
+            stage1 >= TuneState::kSchedules || backfill > kMaxBackfill || (cap > 0 && backfill == 0))
             return MRT_ERR_INVALID_ARG;
         // one-shot is a grid of one ray per lane; the deal's blocks are the one-shot kernels'
-        if ((oneshot && backfill != 1) || (deal != 0 && (!oneshot || deal < TuneState::kTuneMinDealBlock ||
-                                                          deal > TuneState::kTuneMaxDealBlock)))
+        if ((oneshot && backfill != 1) ||
+            (block != 0 && (!oneshot || block < deal::kMinBlockLog2 || block > deal::kMaxBlockLog2)))
             return MRT_ERR_INVALID_ARG;
         // a backfilled grid is for the static schedules only: no workgroup of theirs waits for another
         const int sched = locked < TuneState::kSchedules ? locked : stage1;

@@ -2,7 +2,9 @@
 // candidate table, the per-key state machine and the per-handle table of settled
 // schedules. Plain C++ with no HIP in it: it consumes "candidate c took x ms" and
 // answers "launch candidate c next, timed or not"; mrt_api.cpp owns the events that
-// measure the times. tests/cpp/tune_driver.cpp runs it on the CPU.
+// measure the times (TuneEvents, tracer.hpp). tests/cpp/tune_driver.cpp runs it on the CPU.
+// The limits a schedule must respect are read where they are defined: kMaxQueues
+// (trace_limits.hpp), kMaxBackfill (launch_plan.hpp), the deal's block range (deal_common.hpp).
 #pragma once
 
 #include <cstdint>
@@ -10,6 +12,9 @@
 #include <utility>
 
 #include "../../include/mrt.h"
+#include "deal_common.hpp"
+#include "launch_plan.hpp"
+#include "trace_limits.hpp"
 
 namespace mrt {
 
@@ -32,8 +37,6 @@ constexpr int kDefaultTailLanes = MRT_DEFAULT_TAIL_LANES;
 // -22 %, profiles/round2_tuning.md); the register budget of the 4-wide kernels
 // is sized for exactly this occupancy.
 constexpr int kStridedWaves = 20;
-constexpr int kTuneMaxQueues = 8;    // trace_kernel.hpp kMaxQueues (mrt_api.cpp asserts it)
-constexpr int kTuneMaxBackfill = 64; // launch_plan.hpp kMaxBackfill (mrt_api.cpp asserts it)
 constexpr int kSecondaryKey = 512;   // tuning keys only: variant | kSecondaryKey for MRT_TRACE_SECONDARY batches
 
 // The launch configuration a trace uses (the fixed rule): the tracer's, except for a
@@ -109,11 +112,10 @@ struct TuneState {
     int info_code(int c) const;
     int export_code() const;
     // mrt_tuned_schedule.candidate: the locked candidate (bits 0-7), the schedule it modifies (8-15),
-    // the backfill k (16-22, at most kTuneMaxBackfill), one-shot (23), the residency cap (24-26) and the
-    // one-shot deal's block log2 (27-30: 0 or 6..15); bit 31 zero. A code from before the one-shot
-    // bits has them zero and means what it meant.
+    // the backfill k (16-22, at most kMaxBackfill), one-shot (23), the residency cap (24-26) and the
+    // one-shot deal's block log2 (27-30: 0 or deal::kMinBlockLog2..kMaxBlockLog2 = 6..15); bit 31 zero.
+    // A code from before the one-shot bits has them zero and means what it meant.
     static constexpr int kBackfillShift = 16, kOneshotShift = 23, kCapShift = 24, kDealShift = 27, kCodeBits = 31;
-    static constexpr int kTuneMinDealBlock = 6, kTuneMaxDealBlock = 15;   // deal_common.hpp (mrt_api.cpp asserts it)
 
 private:
     int pick(int incumbent, int first, int last) const;

@@ -129,7 +129,7 @@ void launch(int rays, int variant, const void* stream) {
 int main(int argc, char** argv) {
     for (double& b : base) b = 1.0;
     for (double& m : modf_) m = 1.0;
-    // the library's defaults (mrt_api.cpp default_cfg) in the fields the tuner reads
+    // the library's defaults (launch_plan.cpp default_cfg) in the fields the tuner reads
     user = mrt_launch_cfg{};
     user.num_queues = -1;
     user.lds_stack = 16;

@@ -1,5 +1,6 @@
 """The launch plan (csrc/launch_plan.cpp) on the CPU: the grid, the residency cap and the spill
-slab of a trace launch, persistent or backfilled (cfg.backfill).
+slab of a trace launch, persistent or backfilled (cfg.backfill), and the launch configuration
+behind mrt_tracer_set_config (defaults, sentinels, valid ranges, waves per CU).
 
 lib/launch_plan_driver (tests/cpp/launch_plan_driver.cpp, built by `make` from launch_plan.cpp
 alone with the host compiler: that it links shows the unit has no HIP in it) prints the plan
@@ -128,6 +129,155 @@ def test_spill_cap_raises_k_and_the_result_fits(rays, k):
 def test_a_smaller_spill_cap_and_none_needed():
     assert plan(786432, 1, entries=48, cap=64 << 20)["backfill"] == 3
     assert plan(16588800, 1, entries=0)["backfill"] == 1   # nothing to spill (the LDS ring holds the stack)
+
+
+# ---------------------------------------------------------------- launch configuration (cfg, waves)
+# What mrt_tracer_set_config does before it touches the handle: resolve the "library default"
+# sentinels, then validate. The expected values are the library's before this code moved out of the
+# HIP glue (default_cfg, the sentinel lines of mrt_tracer_set_config, valid_cfg, grid_waves_per_cu).
+DEFAULTS = dict(waves_per_cu=0, fetch_threshold=0, num_queues=-1, lds_stack=16, lane_groups=1, wide=1, spec_slack=2,
+                static_rounds=1, autotune=1, tail_lanes=16, queue_shared=0, queue_block=0, ray_sort=0, queue_xcc_mask=0,
+                backfill=0, oneshot=0, deal_block=0)
+
+
+def cfg(**fields):
+    """(accepted, the resolved configuration) of the default configuration with `fields` set."""
+    (tag, kv, _), = run(PLAN_DRIVER, "cfg", *[f"{k}={v}" for k, v in fields.items()])
+    assert tag == "cfg"
+    out = {k: int(v) for k, v in kv.items()}
+    return out.pop("rc") == 0, out
+
+
+def ids(c):
+    return ",".join(f"{k}={v}" for k, v in c.items()) or "defaults"
+
+
+def test_default_configuration():
+    assert cfg() == (True, DEFAULTS)
+    assert len(DEFAULTS) == 17   # every field of mrt_launch_cfg (the driver asserts its own list against the struct)
+
+
+@pytest.mark.parametrize("field", ["waves_per_cu", "num_queues", "lds_stack", "lane_groups", "static_rounds"])
+def test_zero_is_the_library_default(field):
+    assert cfg(**{field: 0}) == (True, DEFAULTS)
+    # and a negative value is no sentinel there: -1 is num_queues' own default, out of range elsewhere
+    ok, c = cfg(**{field: -1})
+    assert c == {**DEFAULTS, field: -1} and ok == (field == "num_queues")
+
+
+@pytest.mark.parametrize("value", [-1, -7])
+@pytest.mark.parametrize("field", ["wide", "spec_slack", "autotune", "tail_lanes", "queue_shared", "queue_block",
+                                   "queue_xcc_mask", "ray_sort", "backfill", "oneshot", "deal_block"])
+def test_negative_is_the_library_default(field, value):
+    assert cfg(**{field: value}) == (True, DEFAULTS)
+
+
+def test_sentinels_resolve_next_to_set_fields_and_fetch_threshold_has_none():
+    assert cfg(backfill=1, oneshot=1, deal_block=11, tail_lanes=-1, lds_stack=0, wide=-1) == \
+        (True, {**DEFAULTS, "backfill": 1, "oneshot": 1, "deal_block": 11})
+    assert cfg(backfill=1, oneshot=-1, deal_block=-1) == (True, {**DEFAULTS, "backfill": 1})
+    assert cfg(fetch_threshold=-1) == (False, {**DEFAULTS, "fetch_threshold": -1})
+    assert cfg(wide=0, autotune=0, tail_lanes=0, spec_slack=0) == \
+        (True, {**DEFAULTS, "wide": 0, "autotune": 0, "tail_lanes": 0, "spec_slack": 0})   # 0 is a value there
+
+
+# The dicts tests/test_gpu_backfill.py and tests/test_gpu_oneshot.py (test_invalid_combinations_are_refused)
+# hand to mrt_tracer_set_config on a device and see refused.
+REFUSED = [dict(backfill=1, num_queues=1), dict(backfill=3, num_queues=8), dict(backfill=1, ray_sort=1), dict(backfill=65),
+           dict(oneshot=1, backfill=0), dict(oneshot=1, backfill=2), dict(oneshot=1, backfill=1, num_queues=1),
+           dict(oneshot=1, backfill=1, ray_sort=1), dict(oneshot=2, backfill=1), dict(oneshot=0, backfill=1, deal_block=10),
+           dict(oneshot=1, backfill=1, deal_block=5), dict(oneshot=1, backfill=1, deal_block=16),
+           dict(oneshot=1, backfill=1, deal_block=1024)]
+
+
+@pytest.mark.parametrize("c", REFUSED, ids=ids)
+def test_invalid_combinations_are_refused(c):
+    assert len(REFUSED) == 13
+    assert cfg(**c) == (False, {**DEFAULTS, **c})   # nothing to resolve in them: refused as given
+
+
+# The configurations the set_config calls of tests/test_gpu_backfill.py, tests/test_gpu_oneshot.py and the
+# ray-sort cases of tests/test_gpu_parity.py (test_launch_configs_do_not_change_results) set.
+ONESHOT = dict(waves_per_cu=4, backfill=1, oneshot=1, autotune=0)
+ACCEPTED = (
+    [dict(waves_per_cu=4, backfill=k, lane_groups=g, tail_lanes=t, autotune=0)
+     for k in (1, 2, 3) for g in (1, 2, 16) for t in (0, 16)] +
+    [dict(waves_per_cu=4, backfill=1, autotune=0), dict(waves_per_cu=8, backfill=1, autotune=0)] +
+    [dict(waves_per_cu=4, backfill=1, lds_stack=8, wide=w, tail_lanes=t, autotune=0) for w, t in ((0, 0), (1, 0), (1, 16))] +
+    [dict(waves_per_cu=4, backfill=k, lds_stack=8, wide=0, autotune=0) for k in (0, 1)] +
+    [dict(waves_per_cu=4 * cap, backfill=1, autotune=0) for cap in (1, 2, 3, 4, 5)] +
+    [dict(autotune=1, waves_per_cu=0, backfill=0, lane_groups=1, num_queues=-1, lds_stack=16, wide=1, tail_lanes=16),
+     dict(backfill=2), dict(backfill=-1)] +
+    [dict(ONESHOT, deal_block=b, lane_groups=g, tail_lanes=t) for b in (0, 6, 10, 13) for g in (1, 2, 16) for t in (0, 16)] +
+    [dict(ONESHOT, deal_block=b) for b in (6, 10, 13)] +
+    [dict(ONESHOT, oneshot=0, deal_block=0), dict(ONESHOT, deal_block=10, lds_stack=8)] +
+    [dict(ONESHOT, deal_block=10, lds_stack=16, wide=1, tail_lanes=t) for t in (0, 16)] +
+    [dict(waves_per_cu=4, lds_stack=16, wide=0, autotune=0, deal_block=0, backfill=k, oneshot=k) for k in (0, 1)] +
+    [dict(autotune=1, waves_per_cu=0, backfill=0, oneshot=0, deal_block=0, lane_groups=1, num_queues=-1, lds_stack=16,
+          wide=1, tail_lanes=16),
+     dict(backfill=1, oneshot=1, deal_block=11), dict(oneshot=-1, deal_block=-1)] +
+    [dict(ray_sort=1), dict(ray_sort=1, tail_lanes=0), dict(ray_sort=1, waves_per_cu=4), dict(ray_sort=1, lane_groups=16),
+     dict(ray_sort=1, waves_per_cu=8, lds_stack=8)])
+
+
+@pytest.mark.parametrize("c", ACCEPTED, ids=ids)
+def test_configurations_the_gpu_tests_set_are_accepted(c):
+    ok, got = cfg(**c)
+    assert ok
+    assert got == {**DEFAULTS, **{k: (DEFAULTS[k] if v < 0 and k != "num_queues" else v) for k, v in c.items()}}
+
+
+# Every range of valid_cfg: the last value inside and the first outside, on each side.
+@pytest.mark.parametrize("field,inside,outside", [
+    ("waves_per_cu", [4, 32], [-1, 1, 3, 33]),                 # 0 (auto) or 4..32
+    ("fetch_threshold", [0, 64], [-1, 65]),
+    ("num_queues", [-1, 1, 8], [-2, 9]),                       # 0 is the sentinel
+    ("lds_stack", [8, 16, 32], [-1, 4, 7, 9, 12, 24, 33, 64]),
+    ("lane_groups", [1, 2, 64], [-1, 3, 63, 65, 128]),         # a power of two up to 64
+    ("wide", [0, 2], [3]),
+    ("spec_slack", [0, 63], [64]),
+    ("static_rounds", [1, 64], [-1, 65]),
+    ("autotune", [0, 1], [2]),
+    ("tail_lanes", [0, 16], [17]),
+    ("queue_shared", [0, 100], [101]),
+    ("queue_block", [0, 64, 1 << 20], [1, 32, 63, 65, 96, (1 << 20) + 1, 1 << 21]),   # 0 or a power of two 64..2^20
+    ("queue_xcc_mask", [0, 15], [16]),
+    ("ray_sort", [0, 1], [2]),
+    ("backfill", [0, 1, 64], [65]),
+    ("oneshot", [0], [1, 2]),                                  # alone: oneshot needs backfill = 1
+    ("deal_block", [0], [6, 15]),                              # alone: the deal's blocks are the one-shot kernels'
+])
+def test_range_limits(field, inside, outside):
+    for v in inside:
+        assert cfg(**{field: v}) == (True, {**DEFAULTS, field: v}), f"{field}={v} refused"
+    for v in outside:
+        assert cfg(**{field: v}) == (False, {**DEFAULTS, field: v}), f"{field}={v} accepted"
+
+
+def test_range_limits_of_the_one_shot_fields():
+    for b, ok in ((0, True), (5, False), (6, True), (15, True), (16, False)):
+        assert cfg(oneshot=1, backfill=1, deal_block=b)[0] == ok, f"deal_block={b}"
+    assert cfg(oneshot=1, backfill=1)[0] and not cfg(oneshot=2, backfill=1)[0]
+    assert not cfg(oneshot=1, backfill=2)[0] and not cfg(oneshot=1, backfill=0)[0]
+
+
+def waves(rays, num_queues, waves_per_cu=0, cus=CUS):
+    (_, _, line), = run(PLAN_DRIVER, "waves", cus, rays, num_queues, waves_per_cu)
+    assert line.split()[0] == "waves"
+    return int(line.split()[1])
+
+
+def test_waves_per_cu_a_batch_gets():
+    """grid_waves_per_cu on 256 CUs, from the library's code before it moved."""
+    for rays in (1, 76800, 524288, 524289, 12582912, 1 << 30):
+        assert waves(rays, -1) == 20              # static rounds: kStridedWaves, whatever the batch
+        assert waves(rays, -1, 12) == 12 and waves(rays, 1, 12) == 12   # an explicit setting, in both modes
+    assert waves(524288, 1) == 32                 # one ray per lane at full occupancy: 32 * 64 * 256 lanes
+    assert waves(524289, 1) == 8                  # one more: 12 rays per lane, at least 8 waves
+    assert waves(3145728, 1) == 16
+    assert waves(12582912, 1) == 32
+    assert waves(1 << 30, 8) == 32                # never above 32
+    assert waves(2048, 1, cus=1) == 32 and waves(2049, 1, cus=0) == 8   # a device reporting no CUs counts as one
 
 
 # ---------------------------------------------------------------- saved schedules (tune_driver)
