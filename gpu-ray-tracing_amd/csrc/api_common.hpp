@@ -1,6 +1,6 @@
 // api_common.hpp — what the C-ABI files (mrt_api.cpp, bind_api.cpp, refit_api.cpp, build_api.cpp,
-// compat_api.cpp) share: the error returns, the device guard, and the owners of the device
-// memory and the events the library allocates.
+// frame_api.cpp, compat_api.cpp) share: the error returns, the device guard, and the owners of
+// the device memory, the stream-ordered scratch and the events the library allocates.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,6 +62,39 @@ struct DeviceBuf {
     hipError_t free() { return p ? hipFree(std::exchange(p, nullptr)) : hipSuccess; }
     T* get() const { return p; }
     explicit operator bool() const { return p != nullptr; }
+};
+
+// Stream-ordered scratch of one call (hipMallocAsync): taken on a stream before the launches
+// that use it, released on the same stream after the last of them, with no host sync and no
+// state shared between calls. release() reports the free's error, for the caller to report
+// after a launch's; the destructor frees what an early return left (its error is dropped).
+// Move-only.
+struct StreamScratch {
+    void* p = nullptr;
+    hipStream_t stream = nullptr;
+    StreamScratch() = default;
+    StreamScratch(StreamScratch&& o) noexcept : p(std::exchange(o.p, nullptr)), stream(o.stream) {}
+    StreamScratch& operator=(StreamScratch&& o) noexcept {
+        if (this != &o) {
+            (void)release();
+            p = std::exchange(o.p, nullptr);
+            stream = o.stream;
+        }
+        return *this;
+    }
+    ~StreamScratch() { (void)release(); }
+    hipError_t alloc(size_t bytes, hipStream_t s) {
+        (void)release();
+        stream = s;
+        const hipError_t e = hipMallocAsync(&p, bytes, s);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    hipError_t release() { return p ? hipFreeAsync(std::exchange(p, nullptr), stream) : hipSuccess; }
+    template <class T>
+    T* as() const {
+        return static_cast<T*>(p);
+    }
 };
 
 // A hipEvent_t, destroyed with its owner. Move-only.

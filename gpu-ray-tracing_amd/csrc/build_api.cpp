@@ -22,12 +22,8 @@ int check_build_count(int64_t numTriangles) {
 
 // The stream-ordered scratch and the phase events of one build, returned on every way out.
 struct BuildTemps {
-    hipStream_t s = nullptr;
-    void* scratch = nullptr;
     mrt::Event ev[5];
-    ~BuildTemps() {
-        if (scratch) (void)hipFreeAsync(scratch, s);
-    }
+    mrt::StreamScratch scratch;   // last: freed on its stream before the events go
 };
 
 }  // namespace
@@ -74,10 +70,9 @@ int mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, 
                  orderAt = skippedAt + 256, offsetsAt = orderAt + aligned((size_t)maxRecords * 4),
                  total = offsetsAt + aligned(((size_t)maxRecords + 1) * 4);
     BuildTemps tmp;
-    tmp.s = s;
-    MRT_HIP(hipMallocAsync(&tmp.scratch, total, s));
+    MRT_HIP(tmp.scratch.alloc(total, s));
     for (mrt::Event& e : tmp.ev) MRT_HIP(e.create());
-    char* base = static_cast<char*>(tmp.scratch);
+    char* base = tmp.scratch.as<char>();
     auto* skippedDev = reinterpret_cast<unsigned long long*>(base + skippedAt);
     auto* orderDev = reinterpret_cast<int32_t*>(base + orderAt);
     auto* offsetsDev = reinterpret_cast<int32_t*>(base + offsetsAt);
@@ -91,7 +86,7 @@ int mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     b.nodes = static_cast<uint32_t*>(nodes);
     b.woop = static_cast<uint32_t*>(woop);
     b.triIndex = triIndex;
-    mrt::lbvh_carve(b, tmp.scratch, primBytes);
+    mrt::lbvh_carve(b, base, primBytes);
 
     // Phase 1: keys and order. Phase 2: hierarchy and emission.
     const bool single = n <= maxLeaf;

@@ -23,7 +23,7 @@ namespace {
 thread_local std::string g_lastError;
 }  // namespace
 
-// Shared with the ray-generation entry points (csrc/raygen_kernel.hip).
+// Shared with every other C-ABI file (through api_common.hpp's fail).
 int api_fail(int code, const std::string& what) {
     g_lastError = what;
     return code;

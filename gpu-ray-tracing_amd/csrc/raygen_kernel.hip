@@ -1,43 +1,35 @@
-// raygen_kernel.hip — the trace's producers and consumer on the device (gfx950):
-// primary rays, AO/diffuse hemisphere rays and the hit count, so a frame
-// (primary -> trace -> AO -> trace) never leaves HBM.
+// raygen_kernel.hip — the kernels around a frame's traces on the device (gfx950), so a frame
+// (primary -> trace -> AO -> trace -> count / reconstruct) never leaves HBM, and their launch
+// functions (raygen_kernel.hpp). The C-ABI that calls them is frame_api.cpp.
 //
-//   mrt_raygen_primary  <- RayGen::primary + rayGenPrimaryKernel (reference RayGen.cc:50-72,
-//                          RayGenKernels.cu:79-113)
-//   mrt_raygen_ao       <- RayGen::ao + rayGenAOKernel (RayGen.cc:77-120, RayGenKernels.cu:117-227)
-//   mrt_count_hits      <- countHitsKernel / launch_countHitsKernel (RendererKernels.cu:112-162,189-)
-//   mrt_reconstruct     <- reconstructKernel / launch_reconstructKernel (RendererKernels.cu:60-108,
-//                          Renderer.cc:421-445)
+//   primary_kernel                    <- rayGenPrimaryKernel (reference RayGenKernels.cu:79-113)
+//   ao_kernel, ao_per_sample_kernel   <- rayGenAOKernel (RayGenKernels.cu:117-227)
+//   ao_blocks[_tiled]_kernel          the same rays for a list of blocks of a frame's ray order
+//   seed_fill_kernel                  a long frame's batch seeds into device memory
+//   count_partial / count_final       <- countHitsKernel (RendererKernels.cu:112-162)
+//   reconstruct[_tiled]_kernel        <- reconstructKernel (RendererKernels.cu:60-108)
 //
-// The per-ray arithmetic is csrc/raygen_common.hpp, the same code the host
-// generator runs. These are streaming kernels (32 B written per ray, 16-48 B
-// read): one thread per output ray, 256-thread blocks, no LDS. The hit count
-// is a shuffle reduction, one partial per block and a one-block final sum (no
-// contended atomics).
-#include <hip/hip_runtime.h>
+// The per-ray arithmetic is csrc/raygen_common.hpp, the same code the host generator runs.
+// These are streaming kernels (32 B written per ray, 16-48 B read) of 256-thread workgroups,
+// one thread per output ray or pixel. ao_blocks_tiled_kernel (16 KB) and reconstruct_tiled_kernel
+// (17 KB) stage shared values through static LDS; the hit count is a shuffle reduction, one
+// partial per block and a one-block final sum (no contended atomics).
+//
+// Each kernel takes its arguments by value as a file-local struct that adds nothing to the launch
+// interface's (PrimaryArgs : PrimaryLaunch, ...): its mangled symbol is then the one it had
+// before the interface existed, so profiles and assembly diffs against older builds match by name.
+#include "raygen_kernel.hpp"
 
 #include <algorithm>
-#include <cstdint>
 
-#include "../../include/mrt.h"
-#include "raygen_common.hpp"
-#include "trace_kernel.hpp"
+#include "../../include/mrt.h"   // MRT_RAY_*
 
 namespace mrt {
 namespace {
 
-constexpr int kThreads = 256;
+using namespace frame;
 
-struct PrimaryArgs {
-    float m[16];   // column-major nscreen-to-world
-    float ox, oy, oz, maxDist;
-    float jx, jy;   // sample position inside the pixel
-    int w, h;
-    const int32_t* indexToPixel;
-    rg::RayRec* rays;
-    int32_t* slotToId;
-    int32_t* idToSlot;
-};
+struct PrimaryArgs : PrimaryLaunch {};
 
 __global__ __launch_bounds__(kThreads) void primary_kernel(PrimaryArgs a) {
     const int task = (int)(blockIdx.x * kThreads + threadIdx.x);
@@ -48,19 +40,7 @@ __global__ __launch_bounds__(kThreads) void primary_kernel(PrimaryArgs a) {
     if (a.idToSlot) a.idToSlot[pixel] = task;
 }
 
-struct AOArgs {
-    const rg::RayRec* inRays;
-    const int2* inResults;   // RayResult viewed as int2 pairs: slot 2*i = {id, t bits}
-    int numInput;
-    const float* normals;
-    int64_t numTris;
-    int numSamples;
-    float maxDist;
-    uint32_t seed;
-    rg::RayRec* outRays;
-    int32_t* outIdToSlot;
-    int32_t* outSlotToId;
-};
+struct AOArgs : AOLaunch {};
 
 __global__ __launch_bounds__(kThreads) void ao_kernel(AOArgs a) {
     const int task = (int)(blockIdx.x * kThreads + threadIdx.x);
@@ -104,24 +84,7 @@ __global__ __launch_bounds__(kThreads) void ao_per_sample_kernel(AOArgs a) {
 // A frame of at most kMaxBatchSeeds batches carries its seeds in the kernel arguments; a
 // longer one reads them from seedTable (device memory, filled on the stream by
 // seed_fill_kernel launches that carry kMaxBatchSeeds seeds each in their arguments).
-constexpr int kMaxBatchSeeds = 256;
-struct AOBlocksArgs {
-    const rg::RayRec* inRays;
-    const int2* inResults;
-    int numInput;
-    const float* normals;
-    int64_t numTris;
-    int numSamples;
-    float maxDist;
-    int batchInputs;          // P: input rays per batch
-    int blockRays;            // B
-    int64_t totalRays;        // numInput * numSamples
-    int64_t outRays;          // output rays of this launch
-    const int32_t* blocks;
-    rg::RayRec* out;
-    uint32_t seeds[kMaxBatchSeeds];
-    const uint32_t* seedTable;   // kSeedTable kernels: one seed per batch of the frame (last: seeds[] stays where it was)
-};
+struct AOBlocksArgs : AOBlocksLaunch {};
 
 template <bool kSeedTable>
 __device__ inline uint32_t batch_seed(const AOBlocksArgs& a, int batch) {
@@ -163,7 +126,6 @@ __global__ __launch_bounds__(kThreads) void ao_blocks_kernel(AOBlocksArgs a) {
 // evaluations) — then each thread writes kTileRays / kThreads rays (coalesced). Same
 // arithmetic, same bits. Four rays per thread: a 2 M-ray shard is 2 025 workgroups, one
 // round of the device, so the dependent load chain is paid once, not four times.
-constexpr int kTileRays = 1024;
 template <bool kSeedTable>
 __global__ __launch_bounds__(kThreads) void ao_blocks_tiled_kernel(AOBlocksArgs a) {
     __shared__ rg::AOBasis basis[kThreads];
@@ -191,266 +153,6 @@ __global__ __launch_bounds__(kThreads) void ao_blocks_tiled_kernel(AOBlocksArgs 
         if (j0 + o >= a.outRays || g0 + o >= a.totalRays) break;
         a.out[j0 + o] = rg::ao_sample_dir(basis[o / S], sample[o % S], a.maxDist);
     }
-}
-
-// mrt_shard_blocks: a rank's blocks of the frame's secondary-ray order (block i to rank
-// i % world) and their trace order. A list of at most kOrderMax blocks: two launches, no host
-// sync (longer lists: the tile kernels below):
-//   block_live_kernel   one wave per listed block: its live rays = the samples of its input
-//                       rays whose primary hit (RayGenKernels.cu:117-227: a missed primary's
-//                       samples get tmax = -1), as the sort key B - live (the frame's partial
-//                       last block: the largest key, so it sorts last);
-//   block_order_kernel  one workgroup: a stable LSD radix sort of the list by that key in LDS
-//                       (three 4-bit digit passes; per-thread digit counts over contiguous chunks
-//                       keep equal keys in list = frame order), then the ordered block ids.
-constexpr int kOrderThreads = 1024;
-constexpr int kOrderMax = 16384;      // list entries the one-workgroup sort holds
-constexpr int kKeyMax = 4095;         // 12-bit keys
-
-struct ShardArgs {
-    const int2* results;     // primary RayResult viewed as int2 pairs
-    int numPrimary, numSamples, blockRays, world, rank, numBlocks;   // numBlocks: listed (this rank's)
-    int64_t totalRays;
-    int32_t* out;            // the block list; first the keys (block_live_kernel), then the ordered ids
-};
-
-__device__ inline int shard_block_id(const ShardArgs& a, int j) { return a.rank + j * a.world; }
-
-__global__ __launch_bounds__(kThreads) void block_live_kernel(ShardArgs a) {
-    const int lane = (int)(threadIdx.x & 63);
-    const int64_t jj = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);   // one wave per entry
-    if (jj >= a.numBlocks) return;
-    const int j = (int)jj;
-    const int64_t g0 = (int64_t)shard_block_id(a, j) * a.blockRays;
-    const int64_t g1 = min(g0 + a.blockRays, a.totalRays);
-    const int64_t p0 = g0 / a.numSamples, p1 = (g1 - 1) / a.numSamples;   // input rays touching the block
-    int live = 0;
-    for (int64_t p = p0 + lane; p <= p1; p += 64) {
-        if (a.results[2 * p].x >= 0) {
-            const int64_t lo = max(g0, p * a.numSamples), hi = min(g1, (p + 1) * a.numSamples);
-            live += (int)(hi - lo);
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) live += __shfl_xor(live, off, 64);
-    if (lane == 0) {
-        int key = a.blockRays - live;   // decreasing live = increasing key
-        if (a.blockRays > kKeyMax - 1)  // quantized to 12 bits (mrt.dist.live_sort_key restates it)
-            key = (int)(((int64_t)key * (kKeyMax - 1) + a.blockRays - 1) / a.blockRays);
-        if (g1 - g0 < a.blockRays) key = kKeyMax;   // the partial last block sorts last
-        a.out[j] = key;
-    }
-}
-
-// Inclusive prefix sum over a wave's 64 lanes in six DPP adds (row_shr 1/2/4/8 within each
-// 16-lane row, then row_bcast 15/31 across rows): VALU only, no LDS permutes.
-__device__ inline int wave_scan_incl(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
-constexpr int kOrderWaves = kOrderThreads / 64;
-#if defined(__HIP_DEVICE_COMPILE__)
-constexpr int kOrderLdsBytes = 3 * kOrderMax * (int)sizeof(uint16_t) + 2 * kOrderWaves * 16 * (int)sizeof(int);
-constexpr int kTileLdsBytes = kOrderLdsBytes + (kKeyMax + 1) * (int)sizeof(int);   // + block_tile_sort_kernel's histogram
-#if defined(__gfx950__)
-constexpr int kDeviceLdsBytes = 160 * 1024;
-#else
-constexpr int kDeviceLdsBytes = 64 * 1024;
-#endif
-static_assert(kTileLdsBytes <= kDeviceLdsBytes,
-              "mrt_shard_blocks' LDS sort (block_order_kernel, block_tile_sort_kernel) holds 16384 list entries in "
-              "about 98-114 KB of static LDS: it needs gfx950's 160 KB per workgroup, and this device target has "
-              "64 KB - build with ARCH=gfx950");
-#endif
-
-// The stable sort of n <= kOrderMax list entries in LDS, by all of one workgroup's threads:
-// key[i] and idx[0][i] = i are set (not yet synchronised); on return idx[src][0..n) is the
-// order (src returned; the caller synchronises before it reads another thread's entries).
-__device__ __forceinline__ int order_tile_in_lds(uint16_t* key, uint16_t (*idx)[kOrderMax],
-                                                 int (*waveTot)[16], int (*wavePre)[16], int n) {
-    constexpr int kWaves = kOrderWaves;
-    static_assert((16 * kWaves) % 64 == 0, "the prefix wave walks (digit, wave) entries 64 at a time");
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int chunk = (n + kOrderThreads - 1) / kOrderThreads;
-    const int lo = min(n, t * chunk), hi = min(n, lo + chunk);
-    int src = 0;
-    for (int shift = 0; shift < 12; shift += 4, src ^= 1) {
-        __syncthreads();
-        // this thread's digit counts over its contiguous chunk of the current order (registers:
-        // the digit selects by compare, no dynamic register indexing)
-        int c[16];
-#pragma unroll
-        for (int e = 0; e < 16; e++) c[e] = 0;
-        for (int i = lo; i < hi; i++) {
-            const int d = (key[idx[src][i]] >> shift) & 15;
-#pragma unroll
-            for (int e = 0; e < 16; e++) c[e] += d == e;
-        }
-        // exclusive offsets in (digit, thread) order: digit totals before d, plus this digit's
-        // counts of the threads before t — a wave scan per digit, the waves' totals through LDS,
-        // their (digit, wave) exclusive prefix by one wave, read back once per digit
-        int pre[16];
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const int v = wave_scan_incl(c[e]);
-            pre[e] = v - c[e];
-            if (lane == 63) waveTot[wave][e] = v;
-        }
-        __syncthreads();
-        if (wave == 0) {   // lane l < 16 * kWaves / 64 ... one entry (digit e, wave w) per step, in order
-            int run = 0;
-            for (int e0 = 0; e0 < 16 * kWaves; e0 += 64) {
-                const int q = e0 + lane, e = q / kWaves, w = q - e * kWaves;
-                const int v = waveTot[w][e];
-                const int incl = wave_scan_incl(v);
-                wavePre[w][e] = run + incl - v;
-                run += __builtin_amdgcn_readlane(incl, 63);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; e++) pre[e] += wavePre[wave][e];
-        for (int i = lo; i < hi; i++) {
-            const uint16_t v = idx[src][i];
-            const int d = (key[v] >> shift) & 15;
-            int pos = 0;
-#pragma unroll
-            for (int e = 0; e < 16; e++) {
-                pos = d == e ? pre[e] : pos;
-                pre[e] += d == e;
-            }
-            idx[src ^ 1][pos] = v;
-        }
-    }
-    return src;
-}
-
-__global__ __launch_bounds__(kOrderThreads) void block_order_kernel(ShardArgs a) {
-    __shared__ uint16_t key[kOrderMax];
-    __shared__ uint16_t idx[2][kOrderMax];
-    __shared__ int waveTot[kOrderWaves][16];
-    __shared__ int wavePre[kOrderWaves][16];
-    const int t = (int)threadIdx.x, n = a.numBlocks;
-    for (int i = t; i < n; i += kOrderThreads) {
-        key[i] = (uint16_t)a.out[i];
-        idx[0][i] = (uint16_t)i;
-    }
-    const int src = order_tile_in_lds(key, idx, waveTot, wavePre, n);
-    __syncthreads();
-    for (int i = t; i < n; i += kOrderThreads) a.out[i] = shard_block_id(a, idx[src][i]);
-}
-
-// Lists longer than kOrderMax (mrt_shard_blocks): three launches after block_live_kernel, each
-// a phase that reads what every workgroup of the one before wrote — the stream orders them;
-// no workgroup ever waits for another.
-//   block_tile_sort_kernel     workgroup = one tile of <= kOrderMax consecutive list entries:
-//                              the LDS sort above; the tile-sorted (key, index in tile) pairs to
-//                              pairs[], the tile's counts per key — read off the run boundaries
-//                              of the sorted keys — to table[key][tile];
-//   block_hist_scan_kernel     one workgroup: table -> its exclusive prefix sum in memory order,
-//                              key-major, tile-minor = where each tile's run of each key starts
-//                              in the sorted list (equal keys: lower tile first, so list order);
-//   block_tile_scatter_kernel  workgroup = tile: entry i of the tile's order, of key k, goes to
-//                              table[k][tile] + (i - the run's first i), as its block id.
-// The keys stay in the list until block_tile_sort_kernel has read them; only the scatter
-// writes block ids there.
-struct TileArgs {
-    ShardArgs s;
-    uint32_t* pairs;   // [s.numBlocks]: key << 16 | index in tile, tile-sorted
-    int32_t* table;    // [kKeyMax + 1][numTiles]
-    int numTiles;
-};
-
-__global__ __launch_bounds__(kOrderThreads) void block_tile_sort_kernel(TileArgs a) {
-    __shared__ uint16_t key[kOrderMax];
-    __shared__ uint16_t idx[2][kOrderMax];
-    __shared__ int waveTot[kOrderWaves][16];
-    __shared__ int wavePre[kOrderWaves][16];
-    __shared__ int count[kKeyMax + 1];
-    const int t = (int)threadIdx.x, tile = (int)blockIdx.x;
-    const int64_t base = (int64_t)tile * kOrderMax;
-    const int n = (int)min((int64_t)kOrderMax, (int64_t)a.s.numBlocks - base);   // the last tile is short
-    if (tile >= a.numTiles || n <= 0) return;                                   // workgroup-uniform
-    for (int i = t; i < n; i += kOrderThreads) {
-        key[i] = (uint16_t)(a.s.out[base + i] & kKeyMax);
-        idx[0][i] = (uint16_t)i;
-    }
-    for (int k = t; k <= kKeyMax; k += kOrderThreads) count[k] = 0;
-    const int src = order_tile_in_lds(key, idx, waveTot, wavePre, n);
-    __syncthreads();
-    const uint16_t* ord = idx[src];
-    for (int i = t; i < n; i += kOrderThreads) {   // a run's last entry: its end
-        const int v = ord[i], k = key[v];
-        a.pairs[base + i] = (uint32_t)k << 16 | (uint32_t)v;
-        if (i + 1 == n || key[ord[i + 1]] != k) count[k] = i + 1;
-    }
-    __syncthreads();
-    for (int i = t; i < n; i += kOrderThreads) {   // a run's first entry: end - start
-        const int k = key[ord[i]];
-        if (i == 0 || key[ord[i - 1]] != k) count[k] -= i;
-    }
-    __syncthreads();
-    for (int k = t; k <= kKeyMax; k += kOrderThreads) a.table[(int64_t)k * a.numTiles + tile] = count[k];
-}
-
-// In place; numTiles rounds of 4 * kOrderThreads = kKeyMax + 1 consecutive entries (so no
-// ragged end), one int4 per thread, the next round's load issued before this round's barriers.
-__global__ __launch_bounds__(kOrderThreads) void block_hist_scan_kernel(int32_t* table, int numTiles) {
-    static_assert(4 * kOrderThreads == kKeyMax + 1, "a round is one int4 per thread");
-    __shared__ int waveTot[kOrderWaves];
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    int4* tv = reinterpret_cast<int4*>(table);
-    int carry = 0;
-    int4 next = numTiles > 0 ? tv[t] : make_int4(0, 0, 0, 0);
-    for (int r = 0; r < numTiles; r++) {
-        const int4 v = next;
-        if (r + 1 < numTiles) next = tv[(int64_t)(r + 1) * kOrderThreads + t];
-        const int sum = v.x + v.y + v.z + v.w;
-        const int incl = wave_scan_incl(sum);
-        if (lane == 63) waveTot[wave] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < kOrderWaves; w++) {
-            const int x = waveTot[w];
-            all += x;
-            before += w < wave ? x : 0;
-        }
-        const int ex = carry + before + incl - sum;
-        tv[(int64_t)r * kOrderThreads + t] = make_int4(ex, ex + v.x, ex + v.x + v.y, ex + v.x + v.y + v.z);
-        carry += all;
-        __syncthreads();   // waveTot is rewritten next round
-    }
-}
-
-__global__ __launch_bounds__(kOrderThreads) void block_tile_scatter_kernel(TileArgs a) {
-    __shared__ int first[kKeyMax + 1];   // per key of the tile: its run's place in the list - its first i
-    const int t = (int)threadIdx.x, tile = (int)blockIdx.x;
-    const int64_t base = (int64_t)tile * kOrderMax;
-    const int n = (int)min((int64_t)kOrderMax, (int64_t)a.s.numBlocks - base);
-    if (tile >= a.numTiles || n <= 0) return;
-    for (int i = t; i < n; i += kOrderThreads) {
-        const int k = (int)(a.pairs[base + i] >> 16) & kKeyMax;
-        if (i == 0 || ((int)(a.pairs[base + i - 1] >> 16) & kKeyMax) != k)
-            first[k] = a.table[(int64_t)k * a.numTiles + tile] - i;
-    }
-    __syncthreads();
-    for (int i = t; i < n; i += kOrderThreads) {
-        const uint32_t p = a.pairs[base + i];
-        const int64_t pos = (int64_t)first[(int)(p >> 16) & kKeyMax] + i;   // every run's first entry set first[]
-        const int64_t j = base + (int)(p & 0xFFFF);
-        if (pos >= 0 && pos < a.s.numBlocks && j < a.s.numBlocks) a.s.out[pos] = shard_block_id(a.s, (int)j);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void block_list_kernel(ShardArgs a) {
-    const int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (j < a.numBlocks) a.out[j] = shard_block_id(a, (int)j);
 }
 
 // Per block: hits among its rays (id >= 0, RendererKernels.cu:131), one partial.
@@ -485,16 +187,7 @@ __global__ __launch_bounds__(kThreads) void count_final_kernel(const int32_t* pa
     }
 }
 
-struct ReconstructArgs {
-    int numRaysPerPrimary, firstPrimary, numPrimary, rayType;
-    const int32_t* primarySlotToId;
-    const int4* primaryResults;
-    const int32_t* batchIdToSlot;   // NULL: identity (the device/host generators' layout)
-    const int4* batchResults;
-    const uint32_t* triMaterialColor;
-    const uint32_t* triShadedColor;
-    uint32_t* pixels;
-};
+struct ReconstructArgs : ReconstructLaunch {};
 
 // fromABGR / toABGR of RendererKernels.cu:38-56 (device variant: truncating, not rounding).
 __device__ inline float4 from_abgr(uint32_t c) {
@@ -579,290 +272,50 @@ __global__ __launch_bounds__(kThreads) void reconstruct_tiled_kernel(Reconstruct
     if (t < nTasks) finish_pixel(a, c, a.firstPrimary + taskBase + t);
 }
 
-int hip_fail(hipError_t e, const char* what) {
-    return api_fail(MRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+template <class K, class A>
+hipError_t launch(K kernel, int grid, int threads, hipStream_t s, const A& a) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)threads), 0, s, a);
+    return hipGetLastError();
 }
-
-// Whether [p, p + bytes) lies in memory the device can address, as far as the runtime can tell
-// without touching the stream: p is registered with it (device, managed or pinned host memory)
-// and, where it reports the allocation's range, the range holds the bytes. False for any other
-// pointer, and when there is no device.
-bool device_memory_holds(const void* p, size_t bytes) {
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();   // a query's failure is an answer, not a launch error
-        return false;
-    }
-    if (at.type == hipMemoryTypeUnregistered) return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;               // registered, but of a kind the runtime gives no range for
-    }
-    return static_cast<const char*>(p) + bytes <= static_cast<const char*>(base) + size;
-}
-
-constexpr int kCountBlocks = 1024;
 
 }  // namespace
-}  // namespace mrt
 
-using namespace mrt;
-
-extern "C" {
-
-int mrt_raygen_primary(const float nscreenToWorld[16], const float origin[3], float maxDist, int32_t w, int32_t h,
-                       const int32_t* indexToPixel, void* rays, int32_t* slotToId, int32_t* idToSlot, void* stream) {
-    return mrt_raygen_primary_subpixel(nscreenToWorld, origin, maxDist, w, h, 0.5f, 0.5f, indexToPixel, rays, slotToId,
-                                       idToSlot, stream);
+hipError_t launch_primary(const PrimaryLaunch& a, int grid, hipStream_t s) {
+    return launch(primary_kernel, grid, kThreads, s, PrimaryArgs{a});
 }
 
-int mrt_raygen_primary_subpixel(const float nscreenToWorld[16], const float origin[3], float maxDist, int32_t w,
-                                int32_t h, float jx, float jy, const int32_t* indexToPixel, void* rays,
-                                int32_t* slotToId, int32_t* idToSlot, void* stream) {
-    if (!nscreenToWorld || !origin || !indexToPixel || !rays) return api_fail(MRT_ERR_INVALID_ARG, "null argument");
-    if (w <= 0 || h <= 0 || (int64_t)w * h > INT32_MAX) return api_fail(MRT_ERR_INVALID_ARG, "bad image size");
-    if (!(jx >= 0.0f && jx < 1.0f && jy >= 0.0f && jy < 1.0f)) return api_fail(MRT_ERR_INVALID_ARG, "subpixel offset outside [0, 1)");
-    PrimaryArgs a{};
-    a.jx = jx;
-    a.jy = jy;
-    for (int i = 0; i < 16; i++) a.m[i] = nscreenToWorld[i];
-    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
-    a.maxDist = maxDist;
-    a.w = w; a.h = h;
-    a.indexToPixel = indexToPixel;
-    a.rays = static_cast<rg::RayRec*>(rays);
-    a.slotToId = slotToId;
-    a.idToSlot = idToSlot;
-    const int n = w * h;
-    hipLaunchKernelGGL(primary_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0,
-                       static_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MRT_OK : hip_fail(e, "raygen primary launch");
+hipError_t launch_ao(const AOLaunch& a, int grid, hipStream_t s) {
+    return launch(a.numSamples > 1 ? ao_per_sample_kernel : ao_kernel, grid, kThreads, s, AOArgs{a});
 }
 
-int mrt_raygen_ao(const void* inRays, const void* inResults, int32_t numInputRays, const float* triNormals,
-                  int64_t numTris, int32_t numSamples, float maxDist, uint32_t seed, void* outRays,
-                  int32_t* outIdToSlot, int32_t* outSlotToId, void* stream) {
-    if (numInputRays < 0 || numSamples < 1) return api_fail(MRT_ERR_INVALID_ARG, "bad ray/sample count");
-    if (numInputRays == 0) return MRT_OK;
-    if (!inRays || !inResults || !outRays || (numTris > 0 && !triNormals))
-        return api_fail(MRT_ERR_INVALID_ARG, "null argument");
-    if ((int64_t)numInputRays * numSamples > INT32_MAX) return api_fail(MRT_ERR_TOO_LARGE, "too many output rays");
-    AOArgs a{};
-    a.inRays = static_cast<const rg::RayRec*>(inRays);
-    a.inResults = static_cast<const int2*>(inResults);
-    a.numInput = numInputRays;
-    a.normals = triNormals;
-    a.numTris = numTris;
-    a.numSamples = numSamples;
-    a.maxDist = maxDist;
-    a.seed = seed;
-    a.outRays = static_cast<rg::RayRec*>(outRays);
-    a.outIdToSlot = outIdToSlot;
-    a.outSlotToId = outSlotToId;
-    if (numSamples > 1) {
-        const int64_t total = (int64_t)numInputRays * numSamples;
-        hipLaunchKernelGGL(ao_per_sample_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                           static_cast<hipStream_t>(stream), a);
-    } else {
-        hipLaunchKernelGGL(ao_kernel, dim3((numInputRays + kThreads - 1) / kThreads), dim3(kThreads), 0,
-                           static_cast<hipStream_t>(stream), a);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MRT_OK : hip_fail(e, "raygen ao launch");
-}
-
-int mrt_raygen_ao_blocks(const void* inRays, const void* inResults, int32_t numInputRays, const float* triNormals,
-                         int64_t numTris, int32_t numSamples, float maxDist, const uint32_t* batchSeeds,
-                         int32_t numBatches, int32_t batchInputRays, const int32_t* blocks, int32_t numBlocks,
-                         int32_t blockRays, int64_t numOutRays, void* outRays, void* stream) {
-    if (numInputRays < 0 || numSamples < 1 || numBlocks < 0 || blockRays < 1 || batchInputRays < 1 || numOutRays < 0)
-        return api_fail(MRT_ERR_INVALID_ARG, "bad ray/sample/block count");
-    const int64_t total = (int64_t)numInputRays * numSamples;
-    if (total > INT32_MAX) return api_fail(MRT_ERR_TOO_LARGE, "too many frame rays");
-    const int64_t needBatches = ((int64_t)numInputRays + batchInputRays - 1) / batchInputRays;
-    if (numBatches < needBatches) return api_fail(MRT_ERR_INVALID_ARG, "fewer batch seeds than batches");
-    const int64_t nb = (total + blockRays - 1) / blockRays;
-    if (numBlocks > nb) return api_fail(MRT_ERR_INVALID_ARG, "more blocks listed than the frame has");
-    if (numOutRays > (int64_t)numBlocks * blockRays || numOutRays < (int64_t)(numBlocks > 0 ? numBlocks - 1 : 0) * blockRays)
-        return api_fail(MRT_ERR_INVALID_ARG, "numOutRays does not match the listed blocks");
-    if (numOutRays == 0) return MRT_OK;
-    if (!inRays || !inResults || !outRays || !blocks || !batchSeeds || (numTris > 0 && !triNormals))
-        return api_fail(MRT_ERR_INVALID_ARG, "null argument");
-    AOBlocksArgs a{};
-    a.inRays = static_cast<const rg::RayRec*>(inRays);
-    a.inResults = static_cast<const int2*>(inResults);
-    a.numInput = numInputRays;
-    a.normals = triNormals;
-    a.numTris = numTris;
-    a.numSamples = numSamples;
-    a.maxDist = maxDist;
-    a.batchInputs = batchInputRays;
-    a.blockRays = blockRays;
-    a.totalRays = total;
-    a.outRays = numOutRays;
-    a.blocks = blocks;
-    a.out = static_cast<rg::RayRec*>(outRays);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool tiled = blockRays % kTileRays == 0 && kTileRays % numSamples == 0 &&
-                       kTileRays / numSamples <= kThreads && numSamples <= kThreads;
-    // tiled: the tile's input rays and its sample points each fit one LDS slot per thread
-    const dim3 grid((unsigned)(tiled ? (numOutRays + kTileRays - 1) / kTileRays : (numOutRays + kThreads - 1) / kThreads));
-    if (needBatches <= kMaxBatchSeeds) {
-        for (int64_t k = 0; k < needBatches; k++) a.seeds[k] = batchSeeds[k];
-        if (tiled) hipLaunchKernelGGL(ao_blocks_tiled_kernel<false>, grid, dim3(kThreads), 0, s, a);
-        else hipLaunchKernelGGL(ao_blocks_kernel<false>, grid, dim3(kThreads), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? MRT_OK : hip_fail(e, "raygen ao blocks launch");
-    }
-    // More batches than the arguments hold: the seeds go to stream-ordered scratch through fill
-    // launches whose arguments carry them (copied at launch, so the caller's array is free on
-    // return; no copy from pageable memory, no host sync), the generator reads them there.
-    uint32_t* table = nullptr;
-    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&table), (size_t)needBatches * sizeof(uint32_t), s);
-    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(batch seeds)");
+hipError_t launch_seed_table(uint32_t* table, const uint32_t* seeds, int64_t count, hipStream_t s) {
     SeedFillArgs f{};
     f.table = table;
-    for (int64_t first = 0; first < needBatches && e == hipSuccess; first += kMaxBatchSeeds) {
+    for (int64_t first = 0; first < count; first += kMaxBatchSeeds) {
         f.first = (int)first;
-        f.count = (int)std::min<int64_t>(kMaxBatchSeeds, needBatches - first);
-        for (int k = 0; k < f.count; k++) f.seeds[k] = batchSeeds[first + k];
-        hipLaunchKernelGGL(seed_fill_kernel, dim3(1), dim3(kMaxBatchSeeds), 0, s, f);
-        e = hipGetLastError();
+        f.count = (int)std::min<int64_t>(kMaxBatchSeeds, count - first);
+        for (int k = 0; k < f.count; k++) f.seeds[k] = seeds[first + k];
+        if (hipError_t e = launch(seed_fill_kernel, 1, kMaxBatchSeeds, s, f)) return e;
     }
-    if (e == hipSuccess) {
-        a.seedTable = table;
-        if (tiled) hipLaunchKernelGGL(ao_blocks_tiled_kernel<true>, grid, dim3(kThreads), 0, s, a);
-        else hipLaunchKernelGGL(ao_blocks_kernel<true>, grid, dim3(kThreads), 0, s, a);
-        e = hipGetLastError();
-    }
-    const hipError_t fr = hipFreeAsync(table, s);
-    if (e != hipSuccess) return hip_fail(e, "raygen ao blocks launch");
-    return fr == hipSuccess ? MRT_OK : hip_fail(fr, "hipFreeAsync(batch seeds)");
+    return hipSuccess;
 }
 
-int mrt_shard_blocks(const void* primaryResults, int32_t numPrimary, int32_t numSamples, int32_t blockRays,
-                     int32_t world, int32_t rank, int32_t order, int32_t* blocks, int32_t capacity, int32_t* numBlocks,
-                     int64_t* numRays, void* stream) {
-    if (numPrimary < 0 || numSamples < 1 || blockRays < 1 || world < 1 || rank < 0 || rank >= world ||
-        (order != 0 && order != 1) || !numBlocks || !numRays)
-        return api_fail(MRT_ERR_INVALID_ARG, "bad shard arguments");
-    const int64_t total = (int64_t)numPrimary * numSamples;
-    if (total > INT32_MAX) return api_fail(MRT_ERR_TOO_LARGE, "too many frame rays");
-    const int64_t nb = (total + blockRays - 1) / blockRays;
-    const int64_t mine = nb > rank ? (nb - 1 - rank) / world + 1 : 0;
-    const bool lastMine = mine > 0 && (nb - 1) % world == rank;
-    *numBlocks = (int32_t)mine;
-    *numRays = mine * blockRays - (lastMine ? nb * blockRays - total : 0);
-    if (mine == 0 || !blocks) return MRT_OK;   // blocks NULL: a size query
-    if (capacity < mine) return api_fail(MRT_ERR_TOO_LARGE, "block list capacity below the shard's blocks");
-    if (order == 1 && !primaryResults) return api_fail(MRT_ERR_INVALID_ARG, "null primary results");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    ShardArgs a{};
-    a.results = static_cast<const int2*>(primaryResults);
-    a.numPrimary = numPrimary;
-    a.numSamples = numSamples;
-    a.blockRays = blockRays;
-    a.world = world;
-    a.rank = rank;
-    a.numBlocks = (int)mine;
-    a.totalRays = total;
-    a.out = blocks;
-    if (order == 0) {
-        hipLaunchKernelGGL(block_list_kernel, dim3((unsigned)((mine + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? MRT_OK : hip_fail(e, "shard block list launch");
-    }
-    const dim3 liveGrid((unsigned)((mine * 64 + kThreads - 1) / kThreads));
-    if (mine <= kOrderMax) {   // the list fits one workgroup's LDS: two launches, no scratch
-        hipLaunchKernelGGL(block_live_kernel, liveGrid, dim3(kThreads), 0, s, a);
-        hipLaunchKernelGGL(block_order_kernel, dim3(1), dim3(kOrderThreads), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? MRT_OK : hip_fail(e, "shard order launch");
-    }
-    // A long list is written by many workgroups over four launches: before anything is taken or
-    // launched, the list the caller gave must really be there — capacity is the caller's word, the
-    // allocation's extent the runtime's — and so must the results it is ordered by.
-    if (!device_memory_holds(blocks, (size_t)mine * sizeof(int32_t)))
-        return api_fail(MRT_ERR_TOO_LARGE, "no device memory of the shard's blocks behind the block list (" +
-                                               std::to_string(mine) + " entries)");
-    if (!device_memory_holds(primaryResults, (size_t)numPrimary * 4 * sizeof(int32_t)))
-        return api_fail(MRT_ERR_INVALID_ARG, "no device memory of numPrimary results behind primaryResults");
-    // Tiles of kOrderMax entries: stream-ordered scratch for the key-by-tile table (first: its
-    // int4 accesses stay aligned) and the tile-sorted pairs, four launches, no host sync.
-    TileArgs ta{};
-    ta.s = a;
-    ta.numTiles = (int)((mine + kOrderMax - 1) / kOrderMax);
-    const size_t tableInts = (size_t)(kKeyMax + 1) * ta.numTiles;
-    void* scratch = nullptr;
-    hipError_t e = hipMallocAsync(&scratch, (tableInts + (size_t)mine) * sizeof(int32_t), s);
-    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(shard order scratch)");
-    ta.table = static_cast<int32_t*>(scratch);
-    ta.pairs = reinterpret_cast<uint32_t*>(ta.table + tableInts);
-    hipLaunchKernelGGL(block_live_kernel, liveGrid, dim3(kThreads), 0, s, a);
-    hipLaunchKernelGGL(block_tile_sort_kernel, dim3(ta.numTiles), dim3(kOrderThreads), 0, s, ta);
-    hipLaunchKernelGGL(block_hist_scan_kernel, dim3(1), dim3(kOrderThreads), 0, s, ta.table, ta.numTiles);
-    hipLaunchKernelGGL(block_tile_scatter_kernel, dim3(ta.numTiles), dim3(kOrderThreads), 0, s, ta);
-    e = hipGetLastError();
-    const hipError_t f = hipFreeAsync(scratch, s);
-    if (e != hipSuccess) return hip_fail(e, "shard order launch");
-    return f == hipSuccess ? MRT_OK : hip_fail(f, "hipFreeAsync(shard order scratch)");
+hipError_t launch_ao_blocks(const AOBlocksLaunch& a, bool tiled, int grid, hipStream_t s) {
+    if (a.seedTable) return launch(tiled ? ao_blocks_tiled_kernel<true> : ao_blocks_kernel<true>, grid, kThreads, s, AOBlocksArgs{a});
+    return launch(tiled ? ao_blocks_tiled_kernel<false> : ao_blocks_kernel<false>, grid, kThreads, s, AOBlocksArgs{a});
 }
 
-int mrt_count_hits(const void* results, int32_t numRays, int32_t* hitCount, void* stream) {
-    if (!hitCount || numRays < 0 || (numRays > 0 && !results)) return api_fail(MRT_ERR_INVALID_ARG, "bad argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int perBlock = ((numRays + kCountBlocks - 1) / kCountBlocks + kThreads - 1) / kThreads * kThreads;
-    const int blocks = perBlock > 0 ? (numRays + perBlock - 1) / perBlock : 0;
-    // Stream-ordered scratch for the per-block partials (no state shared between calls).
-    int32_t* partial = nullptr;
-    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&partial), (size_t)(blocks + 1) * sizeof(int32_t), s);
-    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(count partials)");
+hipError_t launch_count_hits(const int4* results, int n, int perBlock, int blocks, int32_t* partial, int32_t* hitCount,
+                             hipStream_t s) {
     if (blocks > 0)
-        hipLaunchKernelGGL(count_partial_kernel, dim3(blocks), dim3(kThreads), 0, s,
-                           static_cast<const int4*>(results), numRays, perBlock, partial);
+        hipLaunchKernelGGL(count_partial_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, results, n, perBlock, partial);
     hipLaunchKernelGGL(count_final_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, hitCount);
-    e = hipGetLastError();
-    const hipError_t f = hipFreeAsync(partial, s);
-    if (e != hipSuccess) return hip_fail(e, "count hits launch");
-    return f == hipSuccess ? MRT_OK : hip_fail(f, "hipFreeAsync(count partials)");
+    return hipGetLastError();
 }
 
-int mrt_reconstruct(int32_t rayType, int32_t numRaysPerPrimary, int32_t firstPrimary, int32_t numPrimary,
-                    const int32_t* primarySlotToId, const void* primaryResults, const int32_t* batchIdToSlot,
-                    const void* batchResults, const uint32_t* triMaterialColor, const uint32_t* triShadedColor,
-                    uint32_t* pixels, void* stream) {
-    if (rayType < MRT_RAY_PRIMARY || rayType > MRT_RAY_DIFFUSE) return api_fail(MRT_ERR_INVALID_ARG, "bad ray type");
-    if (numRaysPerPrimary < 1 || firstPrimary < 0 || numPrimary < 0 ||
-        (rayType == MRT_RAY_PRIMARY && numRaysPerPrimary != 1))
-        return api_fail(MRT_ERR_INVALID_ARG, "bad batch shape");
-    if ((int64_t)numPrimary * numRaysPerPrimary > INT32_MAX || (int64_t)firstPrimary + numPrimary > INT32_MAX)
-        return api_fail(MRT_ERR_TOO_LARGE, "too many rays");
-    if (numPrimary == 0) return MRT_OK;
-    if (!primarySlotToId || !primaryResults || !batchResults || !pixels ||
-        (rayType != MRT_RAY_AO && !triShadedColor) || (rayType == MRT_RAY_DIFFUSE && !triMaterialColor))
-        return api_fail(MRT_ERR_INVALID_ARG, "null argument");
-    ReconstructArgs a{};
-    a.numRaysPerPrimary = numRaysPerPrimary;
-    a.firstPrimary = firstPrimary;
-    a.numPrimary = numPrimary;
-    a.rayType = rayType;
-    a.primarySlotToId = primarySlotToId;
-    a.primaryResults = static_cast<const int4*>(primaryResults);
-    a.batchIdToSlot = batchIdToSlot;
-    a.batchResults = static_cast<const int4*>(batchResults);
-    a.triMaterialColor = triMaterialColor;
-    a.triShadedColor = triShadedColor;
-    a.pixels = pixels;
-    const dim3 grid((numPrimary + kThreads - 1) / kThreads);
-    if (rayType != MRT_RAY_PRIMARY && !batchIdToSlot)
-        hipLaunchKernelGGL(reconstruct_tiled_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-    else
-        hipLaunchKernelGGL(reconstruct_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MRT_OK : hip_fail(e, "reconstruct launch");
+hipError_t launch_reconstruct(const ReconstructLaunch& a, int grid, hipStream_t s) {
+    const bool tiled = a.rayType != MRT_RAY_PRIMARY && !a.batchIdToSlot;
+    return launch(tiled ? reconstruct_tiled_kernel : reconstruct_kernel, grid, kThreads, s, ReconstructArgs{a});
 }
 
-}  // extern "C"
+}  // namespace mrt
