@@ -23,7 +23,8 @@
 // every dependency is a kernel boundary (the per-XCD L2 reason of refit_kernel.hip).
 //
 // Built WITHOUT -fgpu-flush-denormals-to-zero and with correctly rounded division
-// (Makefile), so the keys are the host's bit for bit. A triangle with a vertex index
+// (Makefile), so the keys are the host's bit for bit, for denormal, infinite and NaN
+// coordinates too (a NaN centroid enters no bounds and quantizes to 0). A triangle with a vertex index
 // outside [0, numVertices) gets code 0 and its vertices are never read. Every index
 // computed from scratch is range-checked before it addresses an output.
 #include "lbvh_kernel.hpp"

@@ -19,7 +19,9 @@
 //
 // This file is built WITHOUT -fgpu-flush-denormals-to-zero (Makefile), and division
 // is hipcc's default correctly rounded one, so every float here is the IEEE value the
-// host computes: the Woop rows come out bit for bit.
+// host computes: the Woop rows come out bit for bit, denormal, infinite and +-0 rows
+// included. Only the bits of a NaN that an operation makes differ (x86 0xFFC00000,
+// gfx950 0x7FC00000). A NaN vertex coordinate enters no box (woop_common.hpp).
 //
 // Every index read from memory is range-checked before it is used as one: a leaf
 // that runs past the Woop array ends there, a triIndex entry or vertex index out of

@@ -9,7 +9,9 @@
 //   woop_guard the serialiser's -0.0 -> +0.0 on the Z row's x (a -0.0 there
 //              would read as a leaf terminator)
 //   box helpers: FW::min / FW::max ((a < b) ? a : b, not fminf) over vertices and
-//              over two child boxes, in the order both refits use.
+//              over two child boxes, in the order both refits use, except that a NaN
+//              operand never enters a box (box_min / box_max): for finite and infinite
+//              input the bits are FW::min's / FW::max's.
 // Both sides are built with -ffp-contract=off; the device file is built without
 // denormal flushing and with hipcc's default correctly rounded division, so
 // fw_rcp's 1 / d is the IEEE quotient on both sides.
@@ -97,11 +99,19 @@ struct Box {
     float lo[3], hi[3];
 };
 
+// FW::min / FW::max with a NaN on either side dropped. Plain (a < b) ? a : b keeps a NaN b
+// and drops a NaN a: a NaN vertex coordinate would become a plane of its leaf's box and of
+// every ancestor that has that child on side 1, and a ray is culled by a NaN plane, so the
+// finite triangles beside it would be hit by nothing. A triangle with a NaN vertex has NaN
+// Woop rows and is hit by nothing itself; its other coordinates still grow the box.
+MRT_HD inline float box_min(float a, float b) { return (a < b || b != b) ? a : b; }
+MRT_HD inline float box_max(float a, float b) { return (a > b || b != b) ? a : b; }
+
 // The box of a triangle, and a box grown by a triangle (AABB::grow per vertex).
 MRT_HD inline void box_grow(Box& b, const float p[3]) {
     for (int k = 0; k < 3; k++) {
-        b.lo[k] = fw_min(b.lo[k], p[k]);
-        b.hi[k] = fw_max(b.hi[k], p[k]);
+        b.lo[k] = box_min(b.lo[k], p[k]);
+        b.hi[k] = box_max(b.hi[k], p[k]);
     }
 }
 MRT_HD inline Box box_empty() {
@@ -112,8 +122,8 @@ MRT_HD inline Box box_empty() {
 MRT_HD inline Box box_union(const Box& a, const Box& b) {
     Box r;
     for (int k = 0; k < 3; k++) {
-        r.lo[k] = fw_min(a.lo[k], b.lo[k]);
-        r.hi[k] = fw_max(a.hi[k], b.hi[k]);
+        r.lo[k] = box_min(a.lo[k], b.lo[k]);
+        r.hi[k] = box_max(a.hi[k], b.hi[k]);
     }
     return r;
 }

@@ -337,6 +337,12 @@ int  mrt_tracer_stack_overflows(mrt_tracer* t, int64_t* count, int32_t reset);
  *     refitted surface areas would choose other children). cfg.wide 2: the quantized array
  *     has no in-place update; it is derived again from the refitted nodes through the
  *     bind-time host path, which makes the call SYNCHRONOUS and slow (results are correct).
+ *     Where a refitted box is not finite (an infinite vertex coordinate) the quantized form
+ *     cannot hold it: the exact array is derived instead (mrt_bind_info.wide_format 1), and
+ *     it stays, updated in place by later refits, until the next bind or set_config.
+ *   - A NaN vertex coordinate enters no box (a NaN plane would cull the finite triangles
+ *     beside it); that triangle's Woop rows are NaN and nothing hits it. An infinite
+ *     coordinate makes its leaf's and every ancestor's box infinite on that side.
  * MRT_ERR_NOT_BOUND before a bind; MRT_ERR_INVALID_ARG when the bound nodes are not a tree
  * (a child ref outside the array, a record reached twice or never). */
 int  mrt_tracer_refit(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,

@@ -1,7 +1,9 @@
 """Shared by tests/test_lbvh.py and tests/test_gpu_build.py: the scenes and edge shapes of
 the linear BVH build, its keys restated in numpy (float32, one rounding per operation), and
 a checker that walks the emitted Compact2 buffers against a top-down restatement of the
-radix tree, independent of the library's binary searches."""
+radix tree, independent of the library's binary searches; and the edge geometry shared with
+tests/test_refit.py and tests/test_gpu_edge_geometry.py: degenerate triangles, scales from
+denormal to overflowing, non-finite vertices, signed zeros (edge_geometry)."""
 import bisect
 import functools
 
@@ -75,20 +77,149 @@ def host_lbvh(kind_or_name, param, max_leaf):
     return v, t, bufs
 
 
+# ---- geometry at the numeric edges ---------------------------------------------------------
+EDGE_GEOMETRY = ["degenerate", "tiny31", "tiny40", "denormal", "huge30", "huge40", "nonfinite", "signed_zero"]
+SEES_NOTHING = ("tiny40", "denormal", "huge40")   # every Woop row is +-0 or NaN: no ray can hit
+EDGE_SCALE = {"tiny31": -31, "tiny40": -40, "denormal": -130, "huge30": 30, "huge40": 40}
+FLT_MIN = np.finfo(np.float32).tiny
+
+
+def _degenerate(v):
+    """120 of the 800 triangles made zero-area: 40 with two equal vertices, 40 collinear, 40 points.
+    The collinear ones are v0, v0 + e, v0 + 2e on a 2^-10 grid, so both edges and every product
+    of the cross product are exact and the determinant is 0, not merely small."""
+    v = v.reshape(-1, 3, 3).copy()
+    pick = np.random.default_rng(5).choice(len(v), 120, replace=False)
+    v[pick[:40], 1] = v[pick[:40], 0]
+    v0 = np.round(v[pick[40:80], 0] * 1024) / 1024
+    e = np.round((v[pick[40:80], 1] - v[pick[40:80], 0]) * 1024) / 1024
+    e[(e == 0).all(1)] = 1 / 1024
+    v[pick[40:80], 0], v[pick[40:80], 1], v[pick[40:80], 2] = v0, v0 + e, v0 + 2 * e
+    v[pick[80:], 1] = v[pick[80:], 2] = v[pick[80:], 0]
+    return v.reshape(-1, 3)
+
+
+def _nonfinite(v):
+    """10 triangles each with NaN in vertex 0's x, NaN in vertex 2's y, +inf in vertex 1's z,
+    -inf in vertex 2's x."""
+    v = v.reshape(-1, 3, 3).copy()
+    pick = np.random.default_rng(6).choice(len(v), 40, replace=False)
+    v[pick[0:10], 0, 0] = np.nan
+    v[pick[10:20], 2, 1] = np.nan
+    v[pick[20:30], 1, 2] = np.inf
+    v[pick[30:40], 2, 0] = -np.inf
+    return v.reshape(-1, 3)
+
+
+def _signed_zero():
+    """A 32 x 32 grid of pairwise disjoint triangles in the plane z = 0 (one per unit cell, inside
+    it), z = -0.0 at a random half of the vertices: a flat scene without overlaps, so no ties."""
+    rng = np.random.default_rng(7)
+    cell = np.stack(np.meshgrid(np.arange(32.0), np.arange(32.0), indexing="ij"), -1).reshape(-1, 1, 2)
+    corner = np.array([[0.1, 0.1], [0.8, 0.15], [0.2, 0.85]]) + rng.uniform(0, 0.1, (1024, 3, 2))
+    v = np.zeros((1024, 3, 3), np.float32)
+    v[:, :, :2] = cell + corner
+    v[:, :, 2] = np.where(rng.permutation(3072).reshape(1024, 3) < 1536, -0.0, 0.0)
+    return v.reshape(-1, 3), np.arange(3072, dtype=np.int32).reshape(-1, 3)
+
+
+def _edge_precondition(kind, v, t):
+    """A fixture that drifts fails here instead of passing vacuously (on the host build, L = 4)."""
+    nodes, woop, tri = mrt.Bvh.build_lbvh(mrt.Scene.from_arrays(v, t), 4).buffers()
+    z, _ = R.leaf_walk(nodes, woop)
+    rows = woop.view(np.float32).reshape(-1, 4)
+    tri_rows = np.stack([rows[z], rows[z + 1], rows[z + 2]], 1).reshape(len(z), 12)
+    if kind == "degenerate":   # a U or V row that a scan of first words would take for a terminator
+        uv = np.concatenate([z + 1, z + 2])
+        assert (woop.reshape(-1, 4)[uv, 0] == R.TERMINATOR).any()
+        assert (tri_rows == 0).all(1).sum() >= 100
+    if kind == "tiny31":
+        assert np.isinf(tri_rows).any()
+    if kind == "tiny40":
+        assert (tri_rows == 0).all()
+    if kind == "denormal":
+        planes = np.abs(R.boxes(nodes))
+        assert ((planes > 0) & (planes < FLT_MIN)).any()            # a flushed plane would be 0
+        assert not np.array_equal(tri[z], np.arange(len(t)))        # flushed keys would all be 0: index order
+    if kind == "huge30":
+        assert np.isfinite(tri_rows).all()
+    if kind == "huge40":
+        assert np.isnan(tri_rows).any(1).all() and np.isfinite(R.boxes(nodes)).all()
+    if kind == "nonfinite":
+        assert np.isnan(tri_rows).any(1).sum() >= 40 and np.isinf(R.boxes(nodes)).any()
+    if kind == "signed_zero":
+        zplanes = R.boxes(nodes)[:, :, 4:]
+        assert (zplanes == 0).all() and np.signbit(zplanes).any() and not np.signbit(zplanes).all()
+
+
+@functools.lru_cache(maxsize=None)
+def edge_geometry(kind):
+    """(vertices, triangles) of geometry at a numeric edge; cached, read-only. All but
+    signed_zero are the 800-triangle soup _soup(800, 21), so they share a topology."""
+    v, t = _soup(800, 21)
+    if kind == "soup":
+        pass
+    elif kind == "degenerate":
+        v = _degenerate(v)
+    elif kind in EDGE_SCALE:
+        v = np.ldexp(v, EDGE_SCALE[kind]).astype(np.float32)   # exact, but for 2^-130's denormals
+    elif kind == "nonfinite":
+        v = _nonfinite(v)
+    elif kind == "signed_zero":
+        v, t = _signed_zero()
+    else:
+        raise KeyError(kind)
+    v = np.ascontiguousarray(v, np.float32)
+    _edge_precondition(kind, v, t)
+    v.setflags(write=False)
+    t.setflags(write=False)
+    return v, t
+
+
+@functools.lru_cache(maxsize=None)
+def host_edge(kind, max_leaf):
+    """(vertices, triangles, (nodes, woop, triIndex)) of the host LBVH of an edge geometry; cached, read-only."""
+    v, t = edge_geometry(kind)
+    bufs = mrt.Bvh.build_lbvh(mrt.Scene.from_arrays(v, t), max_leaf).buffers()
+    for a in bufs:
+        a.setflags(write=False)
+    return v, t, bufs
+
+
+@functools.lru_cache(maxsize=None)
+def edge_rays(kind):
+    """The 64 x 48 frame of refit_util.frame_rays on the geometry's own scale; read-only. A
+    camera cannot be fitted to non-finite vertices: that kind is seen from the soup's camera."""
+    rays = R.frame_rays(edge_geometry("soup" if kind == "nonfinite" else kind)[0])
+    rays.setflags(write=False)
+    return rays
+
+
+def edge_min_hits(kind):
+    """16 where the frame must see the geometry; 0 where no ray can hit (SEES_NOTHING)."""
+    return 0 if kind in SEES_NOTHING else 16
+
+
 # ---- the keys in numpy -------------------------------------------------------------------
 def np_codes(v, t):
-    """The 63-bit Morton code per triangle as Python-int-exact uint64."""
+    """The 63-bit Morton code per triangle as Python-int-exact uint64, after the comments of
+    lbvh_common.hpp: the centroid is (bmin + bmax) * 0.5 with bmin / bmax folded over vertices
+    0, 1, 2 by (a < b) ? a : b; a NaN centroid never enters the bounds; q is 0 unless ext > 0,
+    else min(2097151, (uint32)((c - lo) / ext * 2097152)) with a NaN to 0."""
     p = np.asarray(v, np.float32)[np.asarray(t)]
-    c = (p.min(1) + p.max(1)) * F(0.5)
-    lo, hi = c.min(0), c.max(0)
-    ext = hi - lo
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        c = (R.fw_min(R.fw_min(p[:, 0], p[:, 1]), p[:, 2]) + R.fw_max(R.fw_max(p[:, 0], p[:, 1]), p[:, 2])) * F(0.5)
+        lo = np.fmin.reduce(c, 0, initial=F(np.inf))    # fmin / fmax drop a NaN
+        hi = np.fmax.reduce(c, 0, initial=F(-np.inf))
+        ext = hi - lo
     code = np.zeros(len(p), np.uint64)
     for k in range(3):
         q = np.zeros(len(p), np.uint64)
         if ext[k] > 0:
-            f = (c[:, k] - lo[k]) / ext[k] * F(2097152.0)
+            with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                f = (c[:, k] - lo[k]) / ext[k] * F(2097152.0)
             assert f.dtype == np.float32
-            q = np.minimum(np.where(f >= 0, f, 0).astype(np.uint64), 2097151).astype(np.uint64)
+            q = np.where(f >= 0, np.minimum(f, F(2097151.0)), F(0)).astype(np.uint64)   # a NaN is not >= 0
         for bit in range(21):
             code |= ((q >> np.uint64(bit)) & np.uint64(1)) << np.uint64(3 * bit + (2 - k))
     return code
@@ -116,9 +247,12 @@ def expected_tree(codes_sorted, max_leaf):
     return {"kept": sorted(kept), "leaves": sorted(leaves)}
 
 
-def check_tree(bufs, v, t, max_leaf):
+def check_tree(bufs, v, t, max_leaf, strict_terminators=True):
     """Every property of the specification that the buffers alone show; returns
-    {"records", "leaves", "slots", "levels"}."""
+    {"records", "leaves", "slots", "levels"}. The terminators and the Z rows' slots are those a
+    walk from the leaf refs finds (refit_util.leaf_walk). strict_terminators: besides, no other
+    slot has a first word 0x80000000; false only for geometry with zero-area triangles or rows
+    that underflow, whose U and V rows may be -0.0."""
     nodes, woop, tri = (np.asarray(a, np.int32) for a in bufs)
     n = len(t)
     rec = nodes.reshape(-1, 16)
@@ -129,8 +263,16 @@ def check_tree(bufs, v, t, max_leaf):
     codes = np_codes(v, t)
     order = np.argsort(codes, kind="stable")            # equal codes stay in index order
     codes_sorted = codes[order]
-    term = (w == R.TERMINATOR).all(1)
-    assert np.array_equal(term, w[:, 0] == R.TERMINATOR)   # a terminator is four words 0x80000000
+    z_slots, term_slots = R.leaf_walk(nodes, woop)
+    assert len(np.unique(z_slots)) == len(z_slots) and len(np.unique(term_slots)) == len(term_slots)
+    assert 3 * len(z_slots) + len(term_slots) == len(w)    # the leaves tile the array
+    term = np.zeros(len(w), bool)
+    term[term_slots] = True
+    assert not term[z_slots].any() and not term[z_slots + 1].any() and not term[z_slots + 2].any()
+    assert (w[term] == R.TERMINATOR).all()                 # a terminator is four words 0x80000000
+    if strict_terminators:
+        assert np.array_equal(term, w[:, 0] == R.TERMINATOR)   # and nothing else starts with that word
+        assert np.array_equal(term, (w == R.TERMINATOR).all(1))
 
     if n <= max_leaf:
         assert len(rec) == 1 and len(w) == 3 * n + 2
@@ -157,7 +299,8 @@ def check_tree(bufs, v, t, max_leaf):
         want_term[3 * (l + 1) + r] = True
     assert np.array_equal(tri, want_tri)                # sorted order at the Z rows' slots, zeros elsewhere
     assert np.array_equal(term, want_term)
-    assert np.array_equal(np.sort(tri[~term][::3]), np.arange(n))   # every triangle in exactly one leaf, once
+    assert np.array_equal(np.nonzero(~term)[0][::3], z_slots)
+    assert np.array_equal(np.sort(tri[z_slots]), np.arange(n))      # every triangle in exactly one leaf, once
     for index, f, l, g in want["kept"]:
         refs = rec[record_of[index], 12:14]
         for ref, (cf, cl, ci) in zip(refs, ((f, g, g), (g + 1, l, g + 1))):

@@ -55,6 +55,7 @@ def _det3(s):
             - s[1][0] * s[2][2] * s[0][1] + s[2][0] * s[0][1] * s[1][2] - s[2][0] * s[0][2] * s[1][1])
 
 
+@np.errstate(all="ignore")   # rows that overflow, underflow or are NaN are results here, not accidents
 def np_woopify(v0, v1, v2):
     """Rows Z, U, V as float32 [n, 12] (guard included) of triangles v0, v1, v2 float32 [n, 3]:
     the cofactor inverse of [v0-v2, v1-v2, cross, v2] with the reference's quirk (d sums
@@ -79,12 +80,46 @@ def np_woopify(v0, v1, v2):
             d = d + dd * a(j, i)
             sj = -sj
         si = -si
-    with np.errstate(divide="ignore", invalid="ignore"):
-        rd = np.where(d != 0, F(1) / d, F(0)).astype(np.float32)
+    rd = np.where(d != 0, F(1) / d, F(0)).astype(np.float32)
     inv = [[(inv[r][c] * rd) * F(4) for c in range(4)] for r in range(4)]
     rows = np.stack([inv[2][0], inv[2][1], inv[2][2], -inv[2][3]] + inv[0] + inv[1], 1).astype(np.float32)
     rows[rows[:, 0] == 0, 0] = 0.0   # -0.0 in Z.x would read as a terminator
     return rows
+
+
+# ---- FW::min / FW::max --------------------------------------------------------------------
+def fw_min(a, b):
+    """(a < b) ? a : b elementwise: a NaN in a is dropped, a NaN in b is kept."""
+    with np.errstate(invalid="ignore"):
+        return np.where(np.asarray(a) < np.asarray(b), a, b).astype(np.float32)
+
+
+def fw_max(a, b):
+    """(a > b) ? a : b elementwise."""
+    with np.errstate(invalid="ignore"):
+        return np.where(np.asarray(a) > np.asarray(b), a, b).astype(np.float32)
+
+
+def box_min(a, b):
+    """woop_common.hpp's box_min: (a < b) ? a : b with a NaN b dropped too, so no NaN enters a box."""
+    with np.errstate(invalid="ignore"):
+        return np.where((np.asarray(a) < np.asarray(b)) | np.isnan(b), a, b).astype(np.float32)
+
+
+def box_max(a, b):
+    with np.errstate(invalid="ignore"):
+        return np.where((np.asarray(a) > np.asarray(b)) | np.isnan(b), a, b).astype(np.float32)
+
+
+FLT_MAX = np.finfo(np.float32).max
+
+
+def fold_box(points):
+    """(lo, hi) of float32 [k, 3] points grown one by one, in order, onto the FLT_MAX-empty box."""
+    lo, hi = np.full(3, FLT_MAX, np.float32), np.full(3, -FLT_MAX, np.float32)
+    for p in points:
+        lo, hi = box_min(lo, p), box_max(hi, p)
+    return lo, hi
 
 
 # ---- Compact2 accessors -----------------------------------------------------------------
@@ -109,10 +144,30 @@ def leaf_slots(woop, ref):
     return out
 
 
+def leaf_walk(nodes, woop):
+    """(z_slots, terminators) as sorted int64 arrays: every leaf ref in the nodes walked from
+    its first slot in steps of three up to the slot whose first word is 0x80000000. Only Z
+    rows are looked at, as the library and the kernels do: a U or V row of a zero-area
+    triangle is (r * 0) * 4, which may be -0.0 in its first word or in all four."""
+    refs = np.ascontiguousarray(nodes).view(np.int32).reshape(-1, 16)[:, 12:14]
+    w0 = np.ascontiguousarray(woop).view(np.int32).reshape(-1, 4)[:, 0]
+    z, term = [], []
+    for ref in refs[refs < 0]:
+        s = ~int(ref)
+        while w0[s] != TERMINATOR:
+            z.append(s)
+            s += 3
+        term.append(s)
+    return np.sort(np.asarray(z, np.int64)), np.sort(np.asarray(term, np.int64))
+
+
 def np_refit(nodes, woop, tri_index, vertices, triangles, skip=()):
-    """(nodes, woop) refitted: every leaf's rows from triIndex -> triangle -> vertices, leaf
-    boxes the min/max of whole triangles, inner boxes unions bottom-up; an empty leaf keeps
-    its box and adds nothing above it. skip: first slots of triangles to leave out (the
+    """(nodes, woop) refitted: every leaf's rows from triIndex -> triangle -> vertices. Boxes
+    are folded with woop_common.hpp's box_min / box_max ((a < b) ? a : b, a NaN dropped) in
+    the library's order: a leaf's triangles in slot order, vertices 0, 1, 2 onto the FLT_MAX-
+    empty box; an inner box is child 0's union child 1's, bottom-up. For finite vertices that
+    is the min / max (a zero's sign is the order's); a NaN coordinate enters no box. An empty
+    leaf keeps its box and adds nothing above it. skip: first slots of triangles to leave out (the
     device refit's treatment of an out-of-range reference: old rows, not in the box)."""
     nodes = np.array(nodes, np.int32).reshape(-1, 16)
     woop = np.array(woop, np.int32).reshape(-1, 4)
@@ -135,12 +190,11 @@ def np_refit(nodes, woop, tri_index, vertices, triangles, skip=()):
                     rows = np_woopify(v[tris[:, 0]], v[tris[:, 1]], v[tris[:, 2]])
                     for s, r in zip(slots, rows):
                         woop[s:s + 3] = r.view(np.int32).reshape(3, 4)
-                    p = v[tris.reshape(-1)]
-                    box = (p.min(0), p.max(0))
+                    box = fold_box(v[tris.reshape(-1)])
             if box is None:
                 continue
             nf[n, box_words(side)] = np.stack([box[0], box[1]], 1).reshape(-1)
-            whole = box if whole is None else (np.minimum(whole[0], box[0]), np.maximum(whole[1], box[1]))
+            whole = box if whole is None else (box_min(whole[0], box[0]), box_max(whole[1], box[1]))
         return whole
 
     import sys
@@ -149,12 +203,44 @@ def np_refit(nodes, woop, tri_index, vertices, triangles, skip=()):
     return nodes.reshape(-1), woop.reshape(-1)
 
 
+def same_bits_or_nan(a, b):
+    """Every 32-bit word equal, or a NaN as float32 on both sides (the payload and sign of a
+    NaN an operation makes differ between x86 and gfx950: 0xFFC00000 and 0x7FC00000)."""
+    a = np.ascontiguousarray(a).view(np.int32)
+    b = np.ascontiguousarray(b).view(np.int32)
+    if a.shape != b.shape:
+        return False
+    fa, fb = a.view(np.float32), b.view(np.float32)
+    return bool(((a == b) | (np.isnan(fa) & np.isnan(fb))).all())
+
+
 def same_nodes(a, b):
-    """Boxes as float values (-0.0 == 0.0), words 12-15 as bits."""
+    """Boxes as float values (-0.0 == 0.0; a NaN equals a NaN), words 12-15 as bits."""
     a = np.ascontiguousarray(a).view(np.int32).reshape(-1, 16)
     b = np.ascontiguousarray(b).view(np.int32).reshape(-1, 16)
-    return a.shape == b.shape and np.array_equal(a[:, 12:], b[:, 12:]) and \
-        np.array_equal(a[:, :12].view(np.float32), b[:, :12].view(np.float32))
+    if a.shape != b.shape or not np.array_equal(a[:, 12:], b[:, 12:]):
+        return False
+    fa, fb = a[:, :12].view(np.float32), b[:, :12].view(np.float32)
+    return bool(((fa == fb) | (np.isnan(fa) & np.isnan(fb))).all())
+
+
+def check_wide(wide_before, wide_after, nodes_before, nodes_after):
+    """The exact 4-wide array after a refit: refs and absent children as before, every present
+    child's planes the refitted Compact2 box the collapse of the ORIGINAL nodes mapped it to."""
+    from mrt.tracer import refit_plan
+    _, _, src = refit_plan(nodes_before)
+    before, after = wide_before.reshape(-1, 32), wide_after.reshape(-1, 32)
+    src = src.reshape(-1, 4)
+    assert len(src) == len(after)
+    assert np.array_equal(after[:, 24:], before[:, 24:])
+    rec = np.ascontiguousarray(nodes_after).view(np.uint32).reshape(-1, 16)
+    for c in range(4):
+        base = [(2 * k + (c >> 1)) * 4 + (c & 1) * 2 + e for k in range(3) for e in (0, 1)]
+        have = src[:, c] >= 0
+        node, side = src[have, c] >> 1, src[have, c] & 1
+        words = np.where(side[:, None] == 0, box_words(0), box_words(1))
+        assert np.array_equal(after[have][:, base], rec[node[:, None], words])
+        assert np.array_equal(after[~have][:, base], before[~have][:, base])   # NaN planes untouched
 
 
 def host_refit(bufs, vertices, triangles):

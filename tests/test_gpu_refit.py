@@ -63,22 +63,7 @@ def moved(name, param):
     return _MOVED[name, param]
 
 
-def check_wide(wide_before, wide_after, nodes_before, nodes_after):
-    """The exact 4-wide array after a refit: refs and absent children as before, every present
-    child's planes the refitted Compact2 box the collapse of the ORIGINAL nodes mapped it to."""
-    _, _, src = refit_plan(nodes_before)
-    before, after = wide_before.reshape(-1, 32), wide_after.reshape(-1, 32)
-    src = src.reshape(-1, 4)
-    assert len(src) == len(after)
-    assert np.array_equal(after[:, 24:], before[:, 24:])
-    rec = np.ascontiguousarray(nodes_after).view(np.uint32).reshape(-1, 16)
-    for c in range(4):
-        base = [(2 * k + (c >> 1)) * 4 + (c & 1) * 2 + e for k in range(3) for e in (0, 1)]
-        have = src[:, c] >= 0
-        node, side = src[have, c] >> 1, src[have, c] & 1
-        words = np.where(side[:, None] == 0, R.box_words(0), R.box_words(1))
-        assert np.array_equal(after[have][:, base], rec[node[:, None], words])
-        assert np.array_equal(after[~have][:, base], before[~have][:, base])   # NaN planes untouched
+check_wide = R.check_wide
 
 
 BIG_LEVEL = ("random", 9000)

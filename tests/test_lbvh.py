@@ -12,6 +12,9 @@ csrc/lbvh_common.hpp), the CPU statement of the device build (mrt_tracer_build).
     displaced vertices equals mrth_bvh_refit;
   * the oracle's traversal of the tree finds what brute force finds;
   * edge shapes: 1, L and L + 1 triangles, 300 copies of one triangle, a flat scene;
+  * geometry at the numeric edges (lbvh_util.edge_geometry: zero-area triangles, scales from
+    denormal to overflowing, NaN and infinite vertices, signed zeros): the same four properties,
+    NaN rows and boxes compared as NaN;
   * the device entry points check their arguments without a device.
 """
 import ctypes as C
@@ -91,6 +94,52 @@ def test_edge_shapes(kind, max_leaf):
     assert R.same_nodes(nodes, bufs[0]) and np.array_equal(woop, bufs[1])
     hits = 1 if kind == "one" else 4
     L.trace_like_brute_force(O, R.frame_rays(v), bufs, min_hits=hits)
+
+
+# ---- geometry at the numeric edges (lbvh_util.edge_geometry) ----------------------------------
+# U and V rows of -0.0 are legitimate where triangles have zero area or the rows underflow.
+LOOSE_TERMINATORS = ("degenerate", "tiny40", "denormal")
+
+
+@pytest.mark.parametrize("max_leaf", [1, 8])
+@pytest.mark.parametrize("kind", L.EDGE_GEOMETRY)
+def test_edge_geometry_host_lbvh_is_the_specified_tree(kind, max_leaf):
+    v, t, bufs = L.host_edge(kind, max_leaf)
+    got = L.check_tree(bufs, v, t, max_leaf, strict_terminators=kind not in LOOSE_TERMINATORS)
+    print(f"{kind} L={max_leaf}: {got}")
+    assert got["records"] == len(bufs[0]) // 16 and got["slots"] == 3 * len(t) + got["leaves"]
+
+
+@pytest.mark.parametrize("kind", L.EDGE_GEOMETRY)
+def test_edge_geometry_leaf_sequence_is_a_stable_argsort_of_the_numpy_keys(kind):
+    """denormal: ext is denormal; nonfinite: centroids and ext are NaN or infinite."""
+    v, t, (nodes, woop, tri) = L.host_edge(kind, 1)
+    z, _ = R.leaf_walk(nodes, woop)
+    codes = L.np_codes(v, t)
+    assert np.array_equal(tri[z], np.argsort(codes, kind="stable"))
+    assert len(np.unique(codes)) > len(t) // 2   # the keys still separate the triangles
+
+
+@pytest.mark.parametrize("max_leaf", [1, 8])
+@pytest.mark.parametrize("kind", L.EDGE_GEOMETRY)
+def test_edge_geometry_refit_is_a_fixed_point(kind, max_leaf):
+    v, t, bufs = L.host_edge(kind, max_leaf)
+    nodes, woop = R.np_refit(*bufs, v, t)
+    assert R.same_nodes(nodes, bufs[0])
+    assert R.same_bits_or_nan(woop, bufs[1])
+    again = R.host_refit(bufs, v, t)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again, bufs))   # one machine: NaNs bit for bit too
+
+
+@pytest.mark.parametrize("max_leaf", [1, 8])
+@pytest.mark.parametrize("kind", L.EDGE_GEOMETRY)
+def test_edge_geometry_oracle_traversal_finds_what_brute_force_finds(kind, max_leaf):
+    _, _, bufs = L.host_edge(kind, max_leaf)
+    got = L.trace_like_brute_force(O, L.edge_rays(kind), bufs, min_hits=L.edge_min_hits(kind))
+    hits = int((got[:, 0] != -1).sum())
+    print(f"{kind} L={max_leaf}: {hits} hits")
+    if kind in L.SEES_NOTHING:   # every Woop row is +-0 or NaN: t is NaN and no ray hits, by construction
+        assert hits == 0
 
 
 def test_default_leaf_size_and_bad_leaf_sizes():

@@ -9,6 +9,9 @@ wide-child source map of the bind-time collapse (csrc/wide_bvh.cpp).
   * moved vertices: the host refit equals a numpy restatement (refit_util.np_refit), and the
     oracle's traversal of the refitted tree finds what brute force over the refitted Woop
     rows finds (t bit for bit, ids up to exact-t ties);
+  * geometry at the numeric edges (lbvh_util.edge_geometry): a refit of the soup's tree to
+    zero-area, scaled, NaN and infinite vertices equals the numpy restatement with NaNs
+    compared as NaNs, traces like brute force, and a refit back restores every byte;
   * plan: every node once, inner children in strictly lower levels, for the serialiser's
     numbering and for a renumbered tree; each mapped Compact2 box is the wide child's planes;
   * errors: an out-of-range vertex index or triIndex entry is refused and nothing is written.
@@ -19,6 +22,7 @@ import numpy as np
 import pytest
 
 import mrt
+import lbvh_util as L
 import oracle_lib as O
 import refit_util as R
 from mrt import _lib
@@ -81,6 +85,39 @@ def test_moved_vertices_trace_like_brute_force(moved):
     assert np.array_equal(got[:, 1], want[:, 1])   # t bit for bit
     diff = np.nonzero(got[:, 0] != want[:, 0])[0]   # two triangles at the same t bits
     assert len(O.invalid_hits(rays, got, woop, tri, which=diff)) == 0
+
+
+# ---- geometry at the numeric edges ------------------------------------------------------
+SOUP_KINDS = [k for k in L.EDGE_GEOMETRY if k != "signed_zero"]   # the soup's topology
+
+
+@pytest.mark.parametrize("max_leaf", [1, 8])
+@pytest.mark.parametrize("kind", SOUP_KINDS)
+def test_refit_to_edge_geometry_equals_the_numpy_restatement(kind, max_leaf):
+    """The soup's tree refitted to collapsed, scaled or non-finite vertices, and back. A NaN
+    coordinate enters no box (it would cull the finite triangles beside it); an infinite one does."""
+    v0, t, bufs = L.host_edge("soup", max_leaf)
+    v, _ = L.edge_geometry(kind)
+    nodes, woop, tri = R.host_refit(bufs, v, t)
+    want_nodes, want_woop = R.np_refit(*bufs, v, t)
+    assert not np.array_equal(woop, bufs[1]), "the refit moved nothing"
+    assert R.same_bits_or_nan(woop, want_woop)
+    assert R.same_nodes(nodes, want_nodes)
+    assert np.array_equal(tri, bufs[2])
+    if kind == "nonfinite":
+        b = R.boxes(nodes)
+        assert not np.isnan(b).any() and np.isinf(b).any()
+    back = R.host_refit((nodes, woop, tri), v0, t)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(back, bufs))   # nothing sticks
+
+
+@pytest.mark.parametrize("kind", SOUP_KINDS)
+def test_refitted_edge_geometry_traces_like_brute_force(kind):
+    _, t, bufs = L.host_edge("soup", 4)
+    refitted = R.host_refit(bufs, L.edge_geometry(kind)[0], t)
+    got = L.trace_like_brute_force(O, L.edge_rays(kind), refitted, min_hits=L.edge_min_hits(kind))
+    if kind in L.SEES_NOTHING:   # every Woop row is +-0 or NaN: no ray hits, by construction
+        assert (got[:, 0] == -1).all()
 
 
 # ---- the plan -------------------------------------------------------------------------
