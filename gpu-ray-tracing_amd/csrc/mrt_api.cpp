@@ -98,6 +98,35 @@ int kernel_key(const mrt::TraceVariant& v) {
     return variant_key(v) | (v.oneshot ? 512 : 0);
 }
 
+// The variant a kernel_key names; false where the key's stack or node-format field has no meaning.
+bool variant_of_key(int key, mrt::TraceVariant* v) {
+    const int lds = (key >> 4) & 3, nodes = (key >> 6) & 3;
+    if (key < 0 || key >= 1024 || lds > 2 || nodes > mrt::kNodeWide4Q) return false;
+    v->anyHit = (key & 1) != 0;
+    v->speculative = (key & 2) != 0;
+    v->exactRcp = (key & 4) != 0;
+    v->stats = (key & 8) != 0;
+    v->ldsStack = 8 << lds;
+    v->nodes = nodes;
+    v->tail = (key & 256) != 0;
+    v->oneshot = (key & 512) != 0;
+    return true;
+}
+
+// The kernel function a key's variant launches (null: none), and the reverse: the smallest key
+// whose variant launches `fn` (-1: none). By the function, not by the variant asked for, so a
+// dispatcher that serves one variant with a sibling's kernel shows (mrt_tracer_last_kernel_key).
+const void* kernel_of_key(int key) {
+    mrt::TraceVariant v{};
+    return variant_of_key(key, &v) ? mrt::trace_kernel_function(v) : nullptr;
+}
+
+int key_of_kernel(const void* fn) {
+    for (int key = 0; fn && key < 1024; key++)
+        if (kernel_of_key(key) == fn) return key;
+    return -1;
+}
+
 // Workgroups per CU the code object of a variant admits (queried once).
 int variant_occupancy(mrt_tracer* t, const mrt::TraceVariant& v) {
     int& occ = t->occ[kernel_key(v)];
@@ -338,6 +367,7 @@ int enqueue_trace(mrt_tracer* t, const mrt::TraceVariant& v, const mrt::TraceArg
     if (blocking) MRT_HIP(hipEventRecord(t->blocking.start, s));
     if (tuneStart) MRT_HIP(hipEventRecord(tuneStart, s));
     MRT_HIP(mrt::launch_trace(v, a, blocks, s, dynLds));
+    t->lastKernel = mrt::trace_kernel_function(v);
 #ifdef MRT_DONE_EVENT
     MRT_HIP(hipEventRecord(ws->done, s));
 #endif
@@ -569,6 +599,23 @@ int mrt_tracer_trace_timed(mrt_tracer* t, const void* rays, void* results, int32
                            int32_t* stats, void* stream, mrt_trace_info* info) {
     mrt_trace_info local;
     return trace_impl(t, rays, results, numRays, flags, stats, stream, info ? info : &local);
+}
+
+int mrt_trace_kernel_keys(int32_t* keys, int capacity) {
+    int n = 0;
+    for (int key = 0; key < 1024; key++) {
+        // a key whose variant is served by the kernel of a smaller key has no kernel of its own
+        if (!kernel_of_key(key) || key_of_kernel(kernel_of_key(key)) != key) continue;
+        if (keys && n < capacity) keys[n] = key;
+        n++;
+    }
+    return n;
+}
+
+int mrt_tracer_last_kernel_key(const mrt_tracer* t) {
+    if (!t) return -1;
+    std::lock_guard<std::mutex> lock(const_cast<mrt_tracer*>(t)->mu);
+    return key_of_kernel(t->lastKernel);
 }
 
 int mrt_tracer_stack_overflows(mrt_tracer* t, int64_t* count, int32_t reset) {

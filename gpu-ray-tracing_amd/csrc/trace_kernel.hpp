@@ -111,6 +111,10 @@ bool build_wide4q(const int32_t* nodes, int64_t numNodes, std::vector<uint32_t>*
 // Whether a variant has a one-shot sibling (launching one that has none is hipErrorInvalidValue).
 bool trace_has_oneshot(const TraceVariant& v);
 
+// The kernel function launch_trace runs for this variant, null where none is instantiated (host
+// only: nothing is launched). Two variants name the same kernel exactly when the pointers are equal.
+const void* trace_kernel_function(const TraceVariant& v);
+
 // Launch one trace. grid = number of 256-thread workgroups: all resident at once (the persistent
 // launch), or more (a backfilled static launch, launch_plan.hpp), then with dynLdsBytes of
 // dynamic LDS per workgroup, which no kernel reads: it only caps how many share a CU.

@@ -121,6 +121,7 @@ struct mrt_tracer {
     static constexpr int kMaxCapBlocks = 8;
     int capDyn[1024][kMaxCapBlocks + 1] = {};
     int staticLds[1024] = {};   // per kernel: its static LDS bytes + 1 (0: not asked yet)
+    const void* lastKernel = nullptr;   // the kernel function of the most recent launch (mrt_tracer_last_kernel_key)
 
     // cfg.autotune: per (batch size, variant) the ray-distribution schedule the
     // measured launches chose (tune.cpp), reset on bind/set_config.

@@ -105,6 +105,8 @@ TRACE_SYMBOLS = [
     ("mrt_tracer_trace", i32, [vp, vp, vp, i32, u32, vp, vp]),
     ("mrt_tracer_trace_timed", i32, [vp, vp, vp, i32, u32, vp, vp, C.POINTER(TraceInfo)]),
     ("mrt_tracer_stack_overflows", i32, [vp, C.POINTER(i64), i32]),
+    ("mrt_trace_kernel_keys", C.c_int, [C.POINTER(i32), C.c_int]),
+    ("mrt_tracer_last_kernel_key", C.c_int, [vp]),
     ("mrt_tracer_refit", i32, [vp, vp, i64, vp, i64, vp]),
     ("mrt_tracer_refit_info", i32, [vp, C.POINTER(RefitInfo)]),
     ("mrt_lbvh_sizes", i32, [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),

@@ -160,6 +160,11 @@ class Tracer:
         _lib.check(self.lib.mrt_tracer_bind_info(self._h, C.byref(b)))
         return {k: getattr(b, k) for k, _ in b._fields_}
 
+    @property
+    def last_kernel_key(self) -> int:
+        """The key (include/mrt.h) of the kernel the most recent trace launched; -1 before any."""
+        return int(self.lib.mrt_tracer_last_kernel_key(self._h))
+
     def schedules(self) -> list:
         """The autotuner's settled schedules [(num_rays, variant, candidate, version)]."""
         n = C.c_int32()

@@ -306,6 +306,29 @@ int  mrt_tracer_trace_timed(mrt_tracer* t, const void* rays, void* results, int3
  * handle's streams (synchronises them). reset != 0 zeroes the counters. */
 int  mrt_tracer_stack_overflows(mrt_tracer* t, int64_t* count, int32_t reset);
 
+/* Which traversal kernel ran, and which exist (host only: neither call touches the device).
+ * A kernel key is a bit field:
+ *   bit 0 (1)    any-hit (MRT_TRACE_ANY_HIT)
+ *   bit 1 (2)    speculative: the warp-wide postponement (MRT_TRACE_LOCKSTEP_OFF clear)
+ *   bit 2 (4)    exact reciprocal (MRT_TRACE_EXACT_RCP)
+ *   bit 3 (8)    per-ray counters (MRT_TRACE_STATS)
+ *   bits 4-5     lds << 4: the LDS stack entries per lane, lds 0 / 1 / 2 = 8 / 16 / 32 (cfg.lds_stack)
+ *   bits 6-7     nodes << 6: the node format read, 0 = Compact2, 1 = exact 4-wide, 2 = quantized 4-wide
+ *   bit 8 (256)  the instantiation with the frontier tail (cfg.tail_lanes > 0; exact 4-wide only)
+ *   bit 9 (512)  the one-shot sibling (cfg.oneshot; exact 4-wide at 16 LDS entries only)
+ * The 4-wide formats exist in the speculative mode only.
+ *
+ * mrt_trace_kernel_keys returns how many kernels the library instantiates and writes the first
+ * `capacity` of their keys, ascending, to keys (which may be NULL with capacity 0): a key is
+ * listed if and only if a launch of that variant has a kernel of its own to run.
+ * mrt_tracer_last_kernel_key returns the key of the kernel the handle's most recent trace
+ * launched: after the autotuner's candidate, after the tail was settled for the bound tree and
+ * after cfg.oneshot fell back where it had to; -1 before any launch (and for a NULL handle).
+ * Both go by the kernel function itself, not by the variant that was asked for: were two
+ * variants served by one function, only the smaller key would be listed and reported. */
+int  mrt_trace_kernel_keys(int32_t* keys, int capacity);
+int  mrt_tracer_last_kernel_key(const mrt_tracer* t);
+
 /* Refit the bound BVH on the device for moved vertices of a FIXED topology (animated or
  * deforming meshes; no reference counterpart). vertices (3 floats each) and triangles (3
  * vertex indices each; the triangles the BVH was built over, triIndex refers to them) are

@@ -75,18 +75,64 @@ def ray(o, d, tmin=0.0, tmax=100.0):
     return np.array([o[0], o[1], o[2], tmin, d[0], d[1], d[2], tmax], np.float32)
 
 
-def scene_two_floors():
+def scene_two_floors(pad=0.0):
     """Root with two leaves.
     leaf A (child 0): tri 7 = unit right triangle in the plane z = 0,
                       tri 3 = the same footprint at z = -2.
     leaf B (child 1): tri 5 = right triangle of leg 2 in the plane z = -1, shifted to x in [2, 4].
+    pad widens leaf A's box in x and y, so that a ray just outside a triangle's edge still
+    reaches the triangle test.
     """
     b = Compact2Builder()
     root = b.reserve_inner()
     A = b.leaf([(7, (0, 0, 0), (1, 0, 0), (0, 1, 0)),
                 (3, (0, 0, -2), (1, 0, -2), (0, 1, -2))])
     B = b.leaf([(5, (2, 0, -1), (4, 0, -1), (2, 2, -1))])
-    b.set_inner(root, ((0, 0, -2), (1, 1, 0)), ((2, 0, -1), (4, 2, -1)), A, B)
+    b.set_inner(root, ((-pad, -pad, -2), (1 + pad, 1 + pad, 0)), ((2, 0, -1), (4, 2, -1)), A, B)
+    return b.buffers()
+
+
+def scene_two_floors_padded():
+    """scene_two_floors with leaf A's box half a unit wider on every side in x and y: the edge
+    and vertex cases are decided by the triangle test's compares, not by a box face."""
+    return scene_two_floors(0.5)
+
+
+def scene_near_second():
+    """Root with two leaves whose boxes and triangles disagree about what is near, for a ray
+    down -z from z = 1 through (0.25, 0.25):
+    child 0: box z = -1 (entered at t = 2), tri 30 in the plane z = -1 (t = 2);
+    child 1: box z in [-3, 0.5] (entered at t = 0.5), tri 31 in the plane z = -3 (t = 4).
+    c1min < c0min, so the binary order enters child 1 first and tests tri 31 before tri 30."""
+    b = Compact2Builder()
+    root = b.reserve_inner()
+    near = b.leaf([(30, (0, 0, -1), (1, 0, -1), (0, 1, -1))])
+    far = b.leaf([(31, (0, 0, -3), (1, 0, -3), (0, 1, -3))])
+    b.set_inner(root, ((0, 0, -1), (1, 1, -1)), ((0, 0, -3), (1, 1, 0.5)), near, far)
+    return b.buffers()
+
+
+def scene_tie_one_leaf():
+    """Two coincident triangles (20 then 21, plane z = -1) in one leaf; the sibling leaf holds
+    tri 22 far to the side."""
+    b = Compact2Builder()
+    root = b.reserve_inner()
+    pair = b.leaf([(20, (0, 0, -1), (1, 0, -1), (0, 1, -1)),
+                   (21, (0, 0, -1), (1, 0, -1), (0, 1, -1))])
+    side = b.leaf([(22, (2, 0, -1), (4, 0, -1), (2, 2, -1))])
+    b.set_inner(root, ((0, 0, -1), (1, 1, -1)), ((2, 0, -1), (4, 2, -1)), pair, side)
+    return b.buffers()
+
+
+def scene_tie_two_leaves():
+    """The same coincident pair, tri 20 in child 0 and tri 21 in child 1, under equal boxes:
+    c0min == c1min, so the binary order does not swap and enters child 0 first."""
+    b = Compact2Builder()
+    root = b.reserve_inner()
+    first = b.leaf([(20, (0, 0, -1), (1, 0, -1), (0, 1, -1))])
+    second = b.leaf([(21, (0, 0, -1), (1, 0, -1), (0, 1, -1))])
+    box = ((0, 0, -1), (1, 1, -1))
+    b.set_inner(root, box, box, first, second)
     return b.buffers()
 
 
@@ -133,6 +179,66 @@ def cases():
                 [(12, 2.0)]))
     out.append(("deep: tmin=2.5 -> farthest", deep, [ray((0.25, 0.25, 0), down, tmin=2.5)], False, [(11, 3.0)]))
     out.append(("deep: from below, nearest is 11", deep, [ray((0.25, 0.25, -5), (0, 0, 1))], False, [(11, 2.0)]))
+    out += boundary_cases()
+    return out
+
+
+def boundary_cases():
+    """The compare boundaries of the reference's tests (t > tmin && t < hitT, u >= 0, v >= 0,
+    u + v <= 1, cmax >= cmin), each from both sides.
+
+    Tri 7 is v0 = (0, 0, 0), v1 = (1, 0, 0), v2 = (0, 1, 0): a point (x, y) of its plane has
+    u = 1 - x - y (along v0 - v2) and v = x (along v1 - v2), so u = 0 is the hypotenuse, v = 0
+    the edge x = 0 and u + v = 1 the edge y = 0; v2 is (u, v) = (0, 0), v0 is (1, 0), v1 is
+    (0, 1). Every coordinate below is a sum of a few powers of two, so u, v and u + v are exact.
+    Tri 3 repeats the footprint at z = -2, so a ray outside an edge fails the same compare twice."""
+    out = []
+    pad = scene_two_floors_padded
+    two = scene_two_floors
+    down = (0, 0, -1)
+    e = 2.0 ** -20
+    for name, xy in (("edge u = 0", (0.5, 0.5)), ("edge v = 0", (0.0, 0.5)), ("edge u + v = 1", (0.5, 0.0)),
+                     ("vertex v2 (u = v = 0)", (0.0, 1.0)), ("vertex v0 (u = 1)", (0.0, 0.0)),
+                     ("vertex v1 (v = 1)", (1.0, 0.0))):
+        out.append((f"{name} hits", pad, [ray((*xy, 1), down)], False, [(7, 1.0)]))
+    for name, xy in (("u = -2^-20", (0.5, 0.5 + e)), ("v = -2^-20", (-e, 0.5)), ("u + v = 1 + 2^-20", (0.5, -e))):
+        out.append((f"outside an edge ({name}) misses", pad, [ray((*xy, 1), down)], False, [(-1, 100.0)]))
+    one = np.float32(1.0)
+    below, above = float(np.nextafter(one, np.float32(0))), float(np.nextafter(one, np.float32(2)))
+    out.append(("t == tmin is excluded: the far floor", two, [ray((0.25, 0.25, 1), down, tmin=1.0)], False, [(3, 3.0)]))
+    out.append(("tmin one ulp below t: found", two, [ray((0.25, 0.25, 1), down, tmin=below)], False, [(7, 1.0)]))
+    out.append(("t == tmax is excluded, tmax kept", two, [ray((0.25, 0.25, 1), down, tmax=1.0)], False, [(-1, 1.0)]))
+    out.append(("tmax one ulp above t: found", two, [ray((0.25, 0.25, 1), down, tmax=above)], False, [(7, 1.0)]))
+    # in the plane z = -2 of tri 3, along +x: Oz = 0 and Dz = 0, t = 0 * inf = NaN fails t > tmin;
+    # tri 7 (Oz = 2, Dz = 0) gives t = inf, which fails t < hitT
+    out.append(("in-plane ray (0 * inf = NaN) misses", two, [ray((-1, 0.25, -2), (1, 0, 0))], False, [(-1, 100.0)]))
+    # from inside leaf A's box between the floors: tri 7 is at t = -0.5, tri 3 at t = 1.5 >= tmax
+    out.append(("hit behind the origin is a miss", two, [ray((0.25, 0.25, -0.5), down, tmax=1.0)], False, [(-1, 1.0)]))
+    out.append(("tmax = +inf: hit", two, [ray((0.25, 0.25, 1), down, tmax=np.inf)], False, [(7, 1.0)]))
+    out.append(("tmax = +inf: miss keeps +inf", two, [ray((8, 8, 1), down, tmax=np.inf)], False, [(-1, np.inf)]))
+    out.append(("direction components of -0.0", two, [ray((0.25, 0.25, 1), (-0.0, -0.0, -1))], False, [(7, 1.0)]))
+    out.append(("closest hit in the child entered second", scene_near_second, [ray((0.25, 0.25, 1), down)], False,
+                [(30, 2.0)]))
+    return out
+
+
+# (name, scene builder, rays, any_hit, per-lane [(id, t)], allowed [{(id, t), ...}]): cases whose answer
+# depends on the order in which triangles are tested. The per-lane Compact2 traversal (and the oracle)
+# tests them in the reference's binary order and gives exactly the per-lane answer (closest hit keeps
+# the first of equal t: the compare is a strict t < hitT); any other kernel may test them in another
+# order and return any member of the allowed set, whose t is still exact.
+def tie_cases():
+    out = []
+    down = (0, 0, -1)
+    r = [ray((0.25, 0.25, 1), down)]
+    pair = [{(20, 2.0), (21, 2.0)}]
+    for any_hit in (False, True):
+        kind = "any" if any_hit else "closest"
+        out.append((f"tie in one leaf ({kind})", scene_tie_one_leaf, r, any_hit, [(20, 2.0)], pair))
+        out.append((f"tie across sibling leaves ({kind})", scene_tie_two_leaves, r, any_hit, [(20, 2.0)], pair))
+    # the any-hit twin of "closest hit in the child entered second": child 1 (tri 31) is entered first
+    out.append(("any-hit returns the first tested, the farther one", scene_near_second, r, True, [(31, 4.0)],
+                [{(30, 2.0), (31, 4.0)}]))
     return out
 
 

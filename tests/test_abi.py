@@ -97,6 +97,49 @@ def test_trace_flags_match_the_header():
         assert getattr(_lib, name) == 1 << int(m.group(1)), name
 
 
+def expected_kernel_keys():
+    """The kernels trace_kernel.hip instantiates, restated from its dispatch rules (include/mrt.h
+    spells the key): Compact2 at every stack size in all 16 flag combinations; the 4-wide formats
+    in the speculative mode only (8 flag combinations), at every stack size, the exact one also
+    with the frontier tail; one-shot siblings of the exact 4-wide kernels at 16 LDS entries."""
+    keys = []
+    for lds in range(3):
+        keys += [flags | lds << 4 for flags in range(16)]                                   # Compact2
+        spec = [flags | lds << 4 for flags in range(16) if flags & 2]
+        keys += [k | 1 << 6 | tail for k in spec for tail in (0, 256)]                      # exact 4-wide
+        keys += [k | 2 << 6 for k in spec]                                                  # quantized 4-wide
+        if lds == 1:
+            keys += [k | 1 << 6 | tail | 512 for k in spec for tail in (0, 256)]            # one-shot
+    return sorted(keys)
+
+
+def test_kernel_key_set_is_the_instantiated_kernels():
+    """mrt_trace_kernel_keys lists exactly the kernels the dispatch rules name: 136, none twice,
+    and nothing the rules exclude (no GPU needed)."""
+    lib = _lib.trace_lib()
+    n = lib.mrt_trace_kernel_keys(None, 0)
+    assert n == 136
+    buf = (C.c_int32 * 1024)()
+    assert lib.mrt_trace_kernel_keys(buf, 1024) == n
+    keys = list(buf[:n])
+    assert len(set(keys)) == n and keys == sorted(keys)
+    assert keys == expected_kernel_keys()
+    short = (C.c_int32 * 5)(*([-7] * 5))
+    assert lib.mrt_trace_kernel_keys(short, 4) == n     # a short buffer gets the first keys only
+    assert list(short) == keys[:4] + [-7]
+    have = set(keys)
+    wide, quant, exact_rcp, lds16, tail, oneshot = 1 << 6, 2 << 6, 4, 1 << 4, 256, 512
+    for absent in (wide | lds16 | exact_rcp,                   # 4-wide without the speculative bit
+                   quant | lds16 | exact_rcp | 1,
+                   wide | 2 | exact_rcp | oneshot,             # one-shot at 8 LDS entries
+                   wide | 2 | exact_rcp | 2 << 4 | oneshot,    # ... and at 32
+                   quant | lds16 | 2 | oneshot, lds16 | 2 | oneshot,
+                   quant | lds16 | 2 | tail, lds16 | 2 | tail,   # the tail outside the exact 4-wide kernels
+                   3 << 4 | 2, 3 << 6 | lds16 | 2, 1024 | lds16 | 2):
+        assert absent not in have, absent
+    assert lib.mrt_tracer_last_kernel_key(None) == -1
+
+
 def test_secondary_hint_travels_with_the_buffer():
     """RayBuffer.secondary reaches the trace flags and survives view() (no GPU needed)."""
     import torch

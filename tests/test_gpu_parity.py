@@ -81,6 +81,21 @@ def test_known_answers(tracer, case, spec, exact):
         assert got[1] == kat.f2i(rt), name
 
 
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("spec", [True, False])
+@pytest.mark.parametrize("case", kat.tie_cases(), ids=lambda c: c[0])
+def test_known_tie_answers(tracer, case, spec, exact):
+    """Order-dependent answers (kat.tie_cases): the per-lane kernel gives the reference's; every
+    other kernel one of the allowed set, with its exact t."""
+    name, scene, rays, any_hit, per_lane, allowed = case
+    res, _ = gpu_trace(tracer, scene(), np.stack(rays), any_hit, exact=exact, spec=spec)
+    for (rid, rt), ok, got in zip(per_lane, allowed, res):
+        if not spec:
+            assert (got[0], got[1]) == (rid, kat.f2i(rt)), name
+        else:
+            assert (got[0], got[1]) in {(i, kat.f2i(t)) for i, t in ok}, name
+
+
 # ---------------------------------------------------------------- golden fixtures
 @pytest.mark.parametrize("fname", sorted(f for f in os.listdir(GOLDEN) if f.endswith(".npz")))
 def test_golden_fixtures(tracer, fname):
@@ -696,6 +711,16 @@ def special_rays(base, seed=7):
     return np.concatenate(groups)
 
 
+def on_surface_rays(base, bufs):
+    """Rays that start on their first hit point (t of the hit along the ray, tmin 0)."""
+    prim, _, _ = O.trace(base, *bufs)
+    hit = np.nonzero(prim[:, 0] >= 0)[0][:192]
+    on = base[hit].copy()
+    on[:, 0:3] = on[:, 0:3] + on[:, 4:7] * prim[hit, 1].view(np.float32)[:, None]
+    on[:, 3] = 0.0
+    return on.astype(np.float32)
+
+
 @pytest.mark.parametrize("scene", ["bunny", "hairball:800", "sponza"])
 def test_special_value_rays(tracer, scene):
     """Edge-value rays (special_rays) traced against the oracle: the per-lane order walks
@@ -703,14 +728,7 @@ def test_special_value_rays(tracer, scene):
     bit-identical whatever the values; the speculative 4-wide mode gives the same
     closest hits and the same any-hit hit/miss."""
     bufs, base, _, _, _ = scene_setup(scene, 64, 48, "primary")
-    rays = special_rays(base)
-    # rays that start on their first hit point (t of the hit along the ray, tmin 0)
-    prim, _, _ = O.trace(base, *bufs)
-    hit = np.nonzero(prim[:, 0] >= 0)[0][:192]
-    on = base[hit].copy()
-    on[:, 0:3] = on[:, 0:3] + on[:, 4:7] * prim[hit, 1].view(np.float32)[:, None]
-    on[:, 3] = 0.0
-    rays = np.concatenate([rays, on.astype(np.float32)])
+    rays = np.concatenate([special_rays(base), on_surface_rays(base, bufs)])
     for any_hit in (False, True):
         want, st, _ = O.trace(rays, *bufs, any_hit=any_hit, stats=True)
         res, gst = gpu_trace(tracer, bufs, rays, any_hit, exact=True, spec=False, stats=True)

@@ -24,6 +24,17 @@ def test_known_answers(case):
     assert (stats[:, 3] == 0).all()
 
 
+@pytest.mark.parametrize("case", kat.tie_cases(), ids=lambda c: c[0])
+def test_known_tie_answers(case):
+    """The oracle walks the reference's binary order: of equal-t candidates it keeps the first
+    tested (strict t < hitT), exactly the per-lane answer, which is one of the allowed set."""
+    name, scene, rays, any_hit, per_lane, allowed = case
+    res, _, _ = O.trace(np.stack(rays), *scene(), any_hit=any_hit)
+    for (rid, rt), ok, got in zip(per_lane, allowed, res):
+        assert (rid, rt) in ok, name
+        assert (got[0], got[1]) == (rid, kat.f2i(rt)), name
+
+
 def test_kat_woop_rows_match_the_product_woopify():
     """mrth_woopify (CudaBVH::woopifyTri restated, with the reference's
     cofactor-inverse quirk) equals the exact inverse on exactly representable triangles."""
