@@ -506,7 +506,13 @@ int  mrt_raygen_primary_subpixel(const float nscreenToWorld[16], const float ori
 /* RayGen::ao + rayGenAOKernel (RayGen.cc:77-120, RayGenKernels.cu:117-227): numSamples
  * hemisphere rays per input ray (origin backed off 1e-4 along the input ray, Halton
  * (2,3) samples rotated by a Jenkins hash of seed + ray index, tmax = -1 for input
- * misses). triNormals: 3 floats per triangle. Closest-hit use (diffuse): maxDist = far. */
+ * misses). triNormals: 3 floats per triangle. Closest-hit use (diffuse): maxDist = far.
+ * Input ids: -1 is a miss (normal (1, 0, 0), tmax = -1). Any other id outside [0, numTris) —
+ * which the reference reads out of bounds — takes the normal (1, 0, 0) too and keeps tmax =
+ * maxDist; triNormals is never read outside its numTris entries. (launch_rayGenAOKernel has no
+ * numTris to pass: there every id but -1 must index triNormals, as in the reference.)
+ * Edge values follow the reference's operations: a NaN t backs off by 0 (fmaxf), a zero normal
+ * gives zero directions (normalize is v * rcp(length), rcp(0) = 0), a NaN normal NaN directions. */
 int  mrt_raygen_ao(const void* inRays, const void* inResults, int32_t numInputRays, const float* triNormals,
                    int64_t numTris, int32_t numSamples, float maxDist, uint32_t seed, void* outRays,
                    int32_t* outIdToSlot, int32_t* outSlotToId, void* stream);
@@ -572,7 +578,9 @@ enum { MRT_RAY_PRIMARY = 0, MRT_RAY_AO = 1, MRT_RAY_DIFFUSE = 2 };
  * batchIdToSlot[pixel id]); batchIdToSlot NULL = identity layout (mrt_raygen_ao's).
  * Results are RayResult (16 B); colour tables one ABGR uint32 per triangle
  * (mrth_scene_tri_colors). Colour arithmetic is the reference's device code: float
- * sums in ray order, truncating toABGR. */
+ * sums in ray order, truncating toABGR.
+ * The caller's contract, as in the reference: every id in primaryResults and batchResults lies
+ * in [-1, entries of the colour tables); the kernels index the tables with it unguarded. */
 int  mrt_reconstruct(int32_t rayType, int32_t numRaysPerPrimary, int32_t firstPrimary, int32_t numPrimary,
                      const int32_t* primarySlotToId, const void* primaryResults, const int32_t* batchIdToSlot,
                      const void* batchResults, const uint32_t* triMaterialColor, const uint32_t* triShadedColor,

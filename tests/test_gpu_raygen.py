@@ -1,6 +1,8 @@
 """Device ray generation and hit counting (mrt_raygen_primary / mrt_raygen_ao /
 mrt_count_hits) against the host generator, which runs the same per-ray code
-(csrc/raygen_common.hpp) on the CPU."""
+(csrc/raygen_common.hpp) on the CPU, and for the AO rays against the numpy restatement
+of the reference's kernel (oracle/raygen_oracle.py) as well; the edges of the inputs
+are in tests/test_gpu_frame_edges.py."""
 import numpy as np
 import pytest
 import torch
@@ -67,6 +69,12 @@ def test_ao_rays_match_the_host(gen, samples):
     # directions go through cosf/sinf (ocml vs glibc): a few ulp
     assert np.abs(dev[:, 4:7] - host[:, 4:7]).max() < 4e-6
     assert np.allclose(np.linalg.norm(dev[:, 4:7], axis=1), 1.0, atol=1e-5)
+    # and against the restatement of the reference's kernel, which shares no code with either
+    import frame_util as U
+    import raygen_oracle as RO
+    want = RO.ao_rays(prim, res, scene.arrays()[2], samples, ao, mrt.AO_SEED, ftz=True)
+    stats = U.compare_ao(dev, want, 1e-5)
+    assert stats["unit_dir"] == stats["rays"] == len(prim) * samples
 
 
 def test_diffuse_frame_on_the_device_matches_the_host_pipeline(gen):
