@@ -10,10 +10,6 @@ using mrt::DeviceGuard;
 using mrt::fail;
 
 namespace mrt {
-namespace {
-// Largest wide-traversal stack a tracer sizes its spill slab for (entries per lane).
-constexpr int kMaxWideStack = 1024;
-}  // namespace
 
 // Synchronous (bind-time work: the Compact2 nodes come to the host, collapse, go back).
 int refresh_wide(mrt_tracer* t) {
@@ -81,19 +77,37 @@ int bind_locked(mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void*
     return rc;
 }
 
+// mrt_tracer_bind's and mrt_tracer_bind_device's argument checks.
+int check_bind_args(const mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
+                    const int32_t* triIndex, int64_t triIndexBytes) {
+    if (!t || !nodes || !woop || !triIndex) return fail(MRT_ERR_INVALID_ARG, "null BVH buffer");
+    if (nodeBytes < 64 || woopBytes < 16 || triIndexBytes < 4 || (nodeBytes % 64) || (woopBytes % 16) ||
+        (triIndexBytes % 4))
+        return fail(MRT_ERR_INVALID_ARG, "BVH buffer sizes are not Compact2-shaped");
+    if (nodeBytes > kMaxBufferBytes || woopBytes > kMaxBufferBytes)
+        return fail(MRT_ERR_TOO_LARGE, "Compact2 buffer above the 32-bit buffer-offset range");
+    if (triIndexBytes / 4 != woopBytes / 16) return fail(MRT_ERR_INVALID_ARG, "triIndex must hold one int per woop float4");
+    return MRT_OK;
+}
+
+// A device bind that refuses its tree leaves the tracer like this too; errors are dropped there.
+void unbind_locked(mrt_tracer* t) {
+    t->bound = false;
+    t->nodes = t->woop = nullptr;
+    t->triIndex = nullptr;
+    DeviceGuard guard(t->device);
+    drop_plan(t);
+    t->wide.builtFor = -1;
+    (void)refresh_wide(t);
+}
+
 }  // namespace mrt
 
 extern "C" {
 
 int mrt_tracer_bind(mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
                     const int32_t* triIndex, int64_t triIndexBytes) {
-    if (!t || !nodes || !woop || !triIndex) return fail(MRT_ERR_INVALID_ARG, "null BVH buffer");
-    if (nodeBytes < 64 || woopBytes < 16 || triIndexBytes < 4 || (nodeBytes % 64) || (woopBytes % 16) ||
-        (triIndexBytes % 4))
-        return fail(MRT_ERR_INVALID_ARG, "BVH buffer sizes are not Compact2-shaped");
-    if (nodeBytes > mrt::kMaxBufferBytes || woopBytes > mrt::kMaxBufferBytes)
-        return fail(MRT_ERR_TOO_LARGE, "Compact2 buffer above the 32-bit buffer-offset range");
-    if (triIndexBytes / 4 != woopBytes / 16) return fail(MRT_ERR_INVALID_ARG, "triIndex must hold one int per woop float4");
+    if (int rc = mrt::check_bind_args(t, nodes, nodeBytes, woop, woopBytes, triIndex, triIndexBytes)) return rc;
     std::lock_guard<std::mutex> lock(t->mu);
     return mrt::bind_locked(t, nodes, nodeBytes, woop, woopBytes, triIndex, triIndexBytes);
 }

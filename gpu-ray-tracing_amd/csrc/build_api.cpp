@@ -26,6 +26,13 @@ struct BuildTemps {
     mrt::StreamScratch scratch;   // last: freed on its stream before the events go
 };
 
+// mrt_tracer_build (onDevice false) and mrt_tracer_build_device: one sequence, the level plan and
+// the bind's derived data made on the host or on the device (derive_api.cpp).
+int build_impl(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,
+               int64_t numTriangles, const mrt_build_params* params, void* nodes, int64_t nodeCapacity, void* woop,
+               int64_t woopCapacity, int32_t* triIndex, int64_t triIndexCapacity, int64_t* nodeBytes,
+               int64_t* woopBytes, int64_t* triIndexBytes, void* stream, bool onDevice);
+
 }  // namespace
 
 extern "C" {
@@ -43,6 +50,33 @@ int mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, 
                      int64_t numTriangles, const mrt_build_params* params, void* nodes, int64_t nodeCapacity,
                      void* woop, int64_t woopCapacity, int32_t* triIndex, int64_t triIndexCapacity,
                      int64_t* nodeBytes, int64_t* woopBytes, int64_t* triIndexBytes, void* stream) {
+    return build_impl(t, vertices, numVertices, triangles, numTriangles, params, nodes, nodeCapacity, woop, woopCapacity,
+                      triIndex, triIndexCapacity, nodeBytes, woopBytes, triIndexBytes, stream, false);
+}
+
+int mrt_tracer_build_device(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,
+                            int64_t numTriangles, const mrt_build_params* params, void* nodes, int64_t nodeCapacity,
+                            void* woop, int64_t woopCapacity, int32_t* triIndex, int64_t triIndexCapacity,
+                            int64_t* nodeBytes, int64_t* woopBytes, int64_t* triIndexBytes, void* stream) {
+    return build_impl(t, vertices, numVertices, triangles, numTriangles, params, nodes, nodeCapacity, woop, woopCapacity,
+                      triIndex, triIndexCapacity, nodeBytes, woopBytes, triIndexBytes, stream, true);
+}
+
+int mrt_tracer_build_info(mrt_tracer* t, mrt_build_info* info) {
+    if (!t || !info) return fail(MRT_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(t->mu);
+    *info = t->lastBuild;
+    return MRT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int build_impl(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,
+               int64_t numTriangles, const mrt_build_params* params, void* nodes, int64_t nodeCapacity, void* woop,
+               int64_t woopCapacity, int32_t* triIndex, int64_t triIndexCapacity, int64_t* nodeBytes,
+               int64_t* woopBytes, int64_t* triIndexBytes, void* stream, bool onDevice) {
     int maxLeaf = params ? params->max_leaf_size : 0;
     if (maxLeaf < 0 || maxLeaf > mrt::lbvh::kMaxLeafLimit) return fail(MRT_ERR_INVALID_ARG, "build: max_leaf_size outside 0..8");
     if (maxLeaf == 0) maxLeaf = MRT_LBVH_DEFAULT_MAX_LEAF;
@@ -105,19 +139,40 @@ int mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, 
         return fail(MRT_ERR_HIP, "build: the emitted counts are inconsistent");
     const int64_t slots = 3 * (int64_t)n + leaves;
 
-    // The level plan of the emitted topology, on the host (the call is synchronous for it).
+    // The level plan of the emitted topology: on the device, kept as the tracer's refit plan, or
+    // on the host (the call is synchronous for it).
     const auto tPlan = std::chrono::steady_clock::now();
-    std::vector<int32_t> host((size_t)records * 16);
-    MRT_HIP(hipMemcpyAsync(host.data(), nodes, host.size() * 4, hipMemcpyDeviceToHost, s));
-    MRT_HIP(hipStreamSynchronize(s));
+    mrt::DeriveRun run;
+    mrt::RefitPlan plan;
     mrt::RefitLevels lv;
-    if (const char* why = mrt::refit_levels(host.data(), records, &lv))
-        return fail(MRT_ERR_HIP, std::string("build: the emitted nodes are not a tree: ") + why);
-    const std::vector<int32_t> offsets(lv.offsets.begin(), lv.offsets.end());
-    MRT_HIP(hipMemcpyAsync(orderDev, lv.order.data(), lv.order.size() * 4, hipMemcpyHostToDevice, s));
-    MRT_HIP(hipMemcpyAsync(offsetsDev, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice, s));
-    MRT_HIP(hipMemsetAsync(skippedDev, 0, sizeof(unsigned long long), s));
-    MRT_HIP(hipStreamSynchronize(s));   // the uploads read lv and offsets
+    bool derived = false;
+    if (onDevice) {
+        int status = mrt::kDeriveOk;
+        const char* why = nullptr;
+        if (int rc = mrt::derive_begin(run, nodes, records, s)) return rc;
+        if (int rc = mrt::derive_plan(run, &plan, s, &status, &why)) return rc;
+        if (status == mrt::kDeriveMalformed)
+            return fail(MRT_ERR_HIP, std::string("build: the emitted nodes are not a tree: ") + why);
+        derived = status == mrt::kDeriveOk;   // else above MRT_DERIVE_MAX_LEVELS depth levels: the host path
+        if (derived) {
+            lv.offsets = plan.levels;
+            orderDev = plan.order.get();
+            offsetsDev = plan.offsets.get();
+            skippedDev = plan.skipped.get();
+        }
+    }
+    if (!derived) {
+        std::vector<int32_t> host((size_t)records * 16);
+        MRT_HIP(hipMemcpyAsync(host.data(), nodes, host.size() * 4, hipMemcpyDeviceToHost, s));
+        MRT_HIP(hipStreamSynchronize(s));
+        if (const char* why = mrt::refit_levels(host.data(), records, &lv))
+            return fail(MRT_ERR_HIP, std::string("build: the emitted nodes are not a tree: ") + why);
+        const std::vector<int32_t> offsets(lv.offsets.begin(), lv.offsets.end());
+        MRT_HIP(hipMemcpyAsync(orderDev, lv.order.data(), lv.order.size() * 4, hipMemcpyHostToDevice, s));
+        MRT_HIP(hipMemcpyAsync(offsetsDev, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice, s));
+        MRT_HIP(hipMemsetAsync(skippedDev, 0, sizeof(unsigned long long), s));
+        MRT_HIP(hipStreamSynchronize(s));   // the uploads read lv and offsets
+    }
     const double planMs = mrt::ms_since(tPlan);
 
     // Phase 3: Woop rows and boxes, by the refit's launches on the buffers not yet bound.
@@ -131,7 +186,7 @@ int mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     a.numVertices = numVertices;
     a.triangles = triangles;
     a.numTriangles = n;
-    a.valid = reinterpret_cast<uint8_t*>(base + validAt);
+    a.valid = derived ? plan.valid.get() : reinterpret_cast<uint8_t*>(base + validAt);
     a.skipped = skippedDev;
     int launches = 0;
     MRT_HIP(hipEventRecord(tmp.ev[3], s));
@@ -140,6 +195,7 @@ int mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     MRT_HIP(hipEventRecord(tmp.ev[4], s));
     unsigned long long skipped = 0;
     MRT_HIP(hipMemcpyAsync(&skipped, skippedDev, sizeof(skipped), hipMemcpyDeviceToHost, s));
+    if (derived) MRT_HIP(hipMemsetAsync(skippedDev, 0, sizeof(skipped), s));   // the kept plan counts refits only
     MRT_HIP(hipStreamSynchronize(s));
 
     mrt_build_info info{};
@@ -147,14 +203,23 @@ int mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     MRT_HIP(hipEventElapsedTime(&info.emit_ms, tmp.ev[1], tmp.ev[2]));
     MRT_HIP(hipEventElapsedTime(&info.fit_ms, tmp.ev[3], tmp.ev[4]));
 
-    if (int rc = mrt::bind_locked(t, nodes, (int64_t)records * 64, woop, slots * 16, triIndex, slots * 4)) return rc;
+    if (derived) {
+        if (int rc = mrt::bind_derived(t, run, std::move(plan), nodes, (int64_t)records * 64, woop, slots * 16, triIndex,
+                                       slots * 4, s)) {
+            mrt::unbind_locked(t);
+            return rc;
+        }
+    } else {
+        if (int rc = mrt::bind_locked(t, nodes, (int64_t)records * 64, woop, slots * 16, triIndex, slots * 4)) return rc;
+        if (onDevice) (void)mrt::derive_report(t, run, false, false, 0.0);
+    }
     info.plan_ms = planMs;
     info.bind_ms = t->bindMs;
     info.levels = lv.levels();
     info.records = records;
     info.leaves = leaves;
     info.slots = slots;
-    info.scratch_bytes = (int64_t)total;
+    info.scratch_bytes = (int64_t)(total + run.scratchBytes);
     info.skipped_refs = (int64_t)skipped;
     info.max_leaf_size = maxLeaf;
     info.wall_ms = mrt::ms_since(t0);
@@ -165,11 +230,4 @@ int mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     return MRT_OK;
 }
 
-int mrt_tracer_build_info(mrt_tracer* t, mrt_build_info* info) {
-    if (!t || !info) return fail(MRT_ERR_INVALID_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(t->mu);
-    *info = t->lastBuild;
-    return MRT_OK;
-}
-
-}  // extern "C"
+}  // namespace

@@ -34,12 +34,45 @@ int upload(DeviceBuf<T>* dst, const std::vector<T>& src) {
     return MRT_OK;
 }
 
-// Builds the refit plan of the bound tree (the handle's mutex held). Synchronous: the
-// Compact2 nodes come to the host once for their child refs (topology only: a refit in
-// flight changes boxes, never words 12-15).
+// The wide source map of a host-derived exact array goes to the device with the plan; a
+// device-derived one is there already (WideArray::srcDev).
+int attach_wide_src(const mrt_tracer* t, RefitPlan* p) {
+    const WideArray& w = t->wide;
+    if (w.nodes && w.format == kNodeWide4 && (int64_t)w.src.size() == w.bytes / 128 * 4) {
+        if (int rc = upload(&p->wideSrc, w.src)) return rc;
+        p->bytes += (int64_t)w.src.size() * 4;
+    } else if (w.nodes && w.format == kNodeWide4 && w.srcDev) {
+        p->bytes += w.bytes / 128 * 4 * 4;
+    }
+    return MRT_OK;
+}
+
+// Builds the refit plan of the bound tree (the handle's mutex held) on the device
+// (derive_api.cpp: no node array crosses to the host). Synchronous. A tree of more than
+// MRT_DERIVE_MAX_LEVELS depth levels takes the host path: the Compact2 nodes come to the host
+// once for their child refs (topology only: a refit in flight changes boxes, never words 12-15).
 int build_plan(mrt_tracer* t) {
     if (t->plan.built) return MRT_OK;
     const int64_t numNodes = t->nodeBytes / 64;
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        DeriveRun r;
+        RefitPlan p;
+        int status = kDeriveOk;
+        const char* why = nullptr;
+        if (int rc = derive_begin(r, t->nodes, numNodes, nullptr)) return rc;
+        if (int rc = derive_plan(r, &p, nullptr, &status, &why)) return rc;
+        if (status == kDeriveMalformed)
+            return fail(MRT_ERR_INVALID_ARG, std::string("refit: the bound nodes are not a tree: ") + why);
+        if (status == kDeriveOk) {
+            MRT_HIP(hipStreamSynchronize(nullptr));   // the offsets' upload reads r
+            drop_plan(t);
+            if (int rc = attach_wide_src(t, &p)) return rc;
+            p.built = true;
+            t->plan = std::move(p);   // complete, or not held at all
+            return derive_report(t, r, true, false, ms_since(t0));
+        }
+    }
     std::vector<int32_t> host((size_t)(t->nodeBytes / 4));
     MRT_HIP(hipMemcpy(host.data(), t->nodes, (size_t)t->nodeBytes, hipMemcpyDeviceToHost));
     RefitLevels lv;
@@ -54,11 +87,7 @@ int build_plan(mrt_tracer* t) {
     MRT_HIP(p.skipped.alloc(sizeof(unsigned long long)));
     MRT_HIP(hipMemset(p.skipped.get(), 0, sizeof(unsigned long long)));
     p.bytes = (int64_t)lv.order.size() * 4 + (int64_t)offsets.size() * 4 + numNodes * 2 + 8;
-    const WideArray& w = t->wide;
-    if (w.nodes && w.format == kNodeWide4 && (int64_t)w.src.size() == w.bytes / 128 * 4) {
-        if (int rc = upload(&p.wideSrc, w.src)) return rc;
-        p.bytes += (int64_t)w.src.size() * 4;
-    }
+    if (int rc = attach_wide_src(t, &p)) return rc;
     p.levels = lv.offsets;
     p.built = true;
     t->plan = std::move(p);   // complete, or not held at all
@@ -123,8 +152,8 @@ int mrt_tracer_refit(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     int launches = 0;
     plan.launched = true;
     if (int rc = mrt::enqueue_refit(a, plan.levels, plan.order.get(), plan.offsets.get(), s, &launches)) return rc;
-    if (plan.wideSrc && wide.nodes && wide.format == mrt::kNodeWide4) {
-        MRT_HIP(mrt::launch_refit_wide(a, plan.wideSrc.get(), wide.nodes.get(), (int)(wide.bytes / 128), s));
+    if (const int32_t* wideSrc = mrt::refit_wide_src(t)) {
+        MRT_HIP(mrt::launch_refit_wide(a, wideSrc, wide.nodes.get(), (int)(wide.bytes / 128), s));
         launches++;
     }
     plan.launches = launches;

@@ -2,7 +2,8 @@
 // another one calls. The handle's sub-objects own their device memory and events; each file
 // works on its own: the handle's lifecycle, configuration, workspace pool, tune events and the
 // trace path (mrt_api.cpp), bind and the 4-wide derivation (bind_api.cpp), refit (refit_api.cpp),
-// the device build (build_api.cpp).
+// the device build (build_api.cpp), the plan and the 4-wide array derived on the device
+// (derive_api.cpp).
 #pragma once
 #include <chrono>
 #include <cstdint>
@@ -13,6 +14,7 @@
 #include "api_common.hpp"
 #include "refit_kernel.hpp"
 #include "tune.hpp"
+#include "wide_kernel.hpp"
 
 namespace mrt {
 
@@ -35,7 +37,13 @@ struct WideArray {
     // copied from, -1 = absent — from the collapse that produced `nodes` (a refit copies the
     // refitted boxes along it; collapsing refitted nodes again would choose other children).
     std::vector<int32_t> src;
+    // The same map where the array was derived on the device (derive_api.cpp): it lives only
+    // there, `src` stays empty, and a refit reads it in place of the plan's copy.
+    DeviceBuf<int32_t> srcDev;
 };
+
+// Largest wide-traversal stack a tracer sizes its spill slab for (entries per lane).
+constexpr int kMaxWideStack = 1024;
 
 // The refit plan (mrt_tracer_refit), built on the first refit after a bind or set_config
 // and dropped by bind, unbind and set_config (drop_plan): the nodes by height level, the wide
@@ -44,7 +52,7 @@ struct RefitPlan {
     bool built = false;
     DeviceBuf<int32_t> order;      // numNodes node indices, level by level
     DeviceBuf<int32_t> offsets;    // levels + 1 offsets into order
-    DeviceBuf<int32_t> wideSrc;    // WideArray::src on the device (null: no exact wide array)
+    DeviceBuf<int32_t> wideSrc;    // WideArray::src on the device (null: no exact wide array, or WideArray::srcDev)
     DeviceBuf<uint8_t> valid;      // 2 per node, rewritten by every refit
     DeviceBuf<unsigned long long> skipped;   // out-of-range references skipped since the last refit_info
     std::vector<int64_t> levels;   // the level offsets on the host
@@ -67,6 +75,21 @@ struct Workspace {
     bool launched = false;        // a launch may still be using this scratch
     uint64_t lastUse = 0;         // launch counter value of the last use (LRU reuse)
 };
+
+// One derivation on the device (derive_api.cpp): its stream-ordered scratch, the depth levels
+// the topology pass found, the phase events and what mrt_tracer_derive_info counts.
+struct DeriveRun {
+    wide::Derive d{};
+    DeriveScratch x{};
+    std::vector<int32_t> depth;      // depth level starts into d.byDepth, depthLevels + 1 entries
+    std::vector<int32_t> offsets32;  // the height level starts, read back from the device
+    int depthLevels = 0;
+    int launches = 0, readbacks = 0;
+    size_t scratchBytes = 0;
+    Event ev[5];                     // topology begin / end, collapse begin, emission begin / end
+    StreamScratch scratch;           // last: freed on its stream before the events go
+};
+enum : int { kDeriveOk = 0, kDeriveMalformed = 1, kDeriveTooDeep = 2 };
 
 // The event pairs of a TuneState's timing slots (created lazily, destroyed in tune_reset).
 struct TuneEvents {
@@ -102,6 +125,7 @@ struct mrt_tracer {
     double bindMs = 0.0;               // wall time of the last bind / wide derivation (mrt_trace_info)
     mrt::RefitPlan plan;
     mrt_build_info lastBuild{};        // the last successful mrt_tracer_build (mrt_tracer_build_info)
+    mrt_derive_info lastDerive{};      // the last device bind / build / plan (mrt_tracer_derive_info)
 
     // Launch scratch, one set per stream the handle has launched on: the stack
     // spill slab, the queue heads and the overflow counter are written by a
@@ -141,6 +165,9 @@ void tune_reset(mrt_tracer* t);
 int bind_locked(mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
                 const int32_t* triIndex, int64_t triIndexBytes);
 int refresh_wide(mrt_tracer* t);
+int check_bind_args(const mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
+                    const int32_t* triIndex, int64_t triIndexBytes);
+void unbind_locked(mrt_tracer* t);
 
 // refit_api.cpp: waits for a refit that may still run (it reads the plan and writes the wide
 // array); forgets the plan; the refit's launches on Compact2 buffers, bound or not.
@@ -148,5 +175,20 @@ int wait_refit(mrt_tracer* t);
 void drop_plan(mrt_tracer* t);
 int enqueue_refit(const RefitArgs& a, const std::vector<int64_t>& levelOffsets, const int32_t* order,
                   const int32_t* offsets, hipStream_t s, int* launches);
+
+// derive_api.cpp: the refit plan and the exact 4-wide array derived on the device (wide_kernel.hip).
+// derive_begin takes the scratch for `numNodes` records at `nodes`; derive_plan fills p (order,
+// offsets, levels, valid, skipped; not wideSrc, not built) and sets *status: kDeriveMalformed
+// with *why = refit_levels' reason, kDeriveTooDeep above MRT_DERIVE_MAX_LEVELS depth levels (the
+// caller takes the host path). bind_derived is bind_locked for a tree whose plan p was derived
+// by r: the bookkeeping, the wide array per cfg.wide, the plan installed. All enqueue on s;
+// bind_derived returns after the device has finished. derive_report fills t->lastDerive.
+int derive_begin(DeriveRun& r, const void* nodes, int64_t numNodes, hipStream_t s);
+int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, int* status, const char** why);
+int bind_derived(mrt_tracer* t, DeriveRun& r, RefitPlan&& p, const void* nodes, int64_t nodeBytes, const void* woop,
+                 int64_t woopBytes, const int32_t* triIndex, int64_t triIndexBytes, hipStream_t s);
+int derive_report(mrt_tracer* t, const DeriveRun& r, bool plan, bool wide, double wallMs);
+// The source map a refit of the exact wide array reads: the plan's copy or the wide array's own.
+const int32_t* refit_wide_src(const mrt_tracer* t);
 
 }  // namespace mrt

@@ -36,6 +36,9 @@
 // box therefore contains the binary box, its slab interval contains the binary
 // one (the slab values are monotonic in the plane), and the traversal tests a
 // superset of the leaves the binary traversal tests.
+//
+// The collapse, the leaf refs and the writing of one exact node are wide_common.hpp's, shared
+// with the kernels that derive the exact form on the device (wide_kernel.hip).
 #include <algorithm>
 #include <atomic>
 #include <thread>
@@ -45,80 +48,20 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <vector>
 
 #include "trace_kernel.hpp"
+#include "wide_common.hpp"
 
 namespace mrt {
 
 namespace {
 
-struct Child {
-    int32_t ref;
-    float lo[3], hi[3];
-    int32_t src;   // the Compact2 slot the box was read from: binary node * 2 + side
-};
+using wide::Child;
+using wide::collapse;
 
-float as_float(int32_t i) {
-    float f;
-    std::memcpy(&f, &i, 4);
-    return f;
-}
-
-void binary_children(const int32_t* nodes, int32_t ref, Child out[2]) {
-    const int32_t* n = nodes + (int64_t)(ref / 4) * 16;
-    const int32_t src = (ref / 4) * 2;
-    out[0] = Child{n[12], {as_float(n[0]), as_float(n[2]), as_float(n[8])}, {as_float(n[1]), as_float(n[3]), as_float(n[9])}, src};
-    out[1] = Child{n[13], {as_float(n[4]), as_float(n[6]), as_float(n[10])}, {as_float(n[5]), as_float(n[7]), as_float(n[11])},
-                   src + 1};
-}
-
-double half_area(const Child& c) {
-    const double x = (double)c.hi[0] - c.lo[0], y = (double)c.hi[1] - c.lo[1], z = (double)c.hi[2] - c.lo[2];
-    return x * y + y * z + z * x;
-}
-
-// The children of the wide node rooted at binary node `ref`.
-int collapse(const int32_t* nodes, int32_t ref, Child out[4]) {
-    Child two[2];
-    binary_children(nodes, ref, two);
-    out[0] = two[0];
-    out[1] = two[1];
-    int n = 2;
-    while (n < 4) {
-        int best = -1;
-        double bestArea = -1.0;
-        for (int i = 0; i < n; i++)
-            if (out[i].ref >= 0 && half_area(out[i]) > bestArea) {
-                bestArea = half_area(out[i]);
-                best = i;
-            }
-        if (best < 0) break;
-        binary_children(nodes, out[best].ref, two);
-        for (int i = n; i > best + 1; i--) out[i] = out[i - 1];   // the two grandchildren take best's place
-        out[best] = two[0];
-        out[best + 1] = two[1];
-        n++;
-    }
-    return n;
-}
-
-// The ref a wide child stores for Compact2 leaf ref `ref` (see above).
-int32_t wide_leaf_ref(int32_t ref, const int32_t* woopX, int64_t woopSlots) {
-    if (!woopX) return ref;
-    const int64_t slot = ~(int64_t)ref;
-    int32_t count = 0;
-    for (int32_t k = 0; k <= 15; k++) {
-        const int64_t s = slot + 3 * (int64_t)k;
-        if (s >= woopSlots) break;
-        if (woopX[s] == (int32_t)0x80000000) {
-            count = k;
-            break;
-        }
-    }
-    return ~(int32_t)(slot | ((int64_t)count << kWideLeafAddrBits));
-}
+static_assert(wide::kSentinel == kEntrypointSentinel && wide::kLeafAddrBits == kWideLeafAddrBits,
+              "wide_common.hpp restates trace_kernel.hpp's constants");
 
 // f32 with denormals flushed to (signed) zero, as the kernel computes.
 float ftz(float x) { return std::fabs(x) < FLT_MIN ? std::copysign(0.0f, x) : x; }
@@ -162,14 +105,15 @@ bool quantize_axis(const float* lo, const float* hi, int n, float* origin, int* 
 }
 
 // The binary roots of the wide nodes under `root` (inclusive), depth first.
-void preorder(const int32_t* nodes, int32_t root, std::vector<int32_t>& order) {
+void preorder(const int32_t* nodes, int64_t numNodes, int32_t root, std::vector<int32_t>& order) {
     std::vector<int32_t> stack{root};
     Child ch[4];
+    bool bad = false;
     while (!stack.empty()) {
         const int32_t ref = stack.back();
         stack.pop_back();
         order.push_back(ref);
-        const int n = collapse(nodes, ref, ch);
+        const int n = collapse(nodes, numNodes, ref, ch, &bad);
         for (int i = n - 1; i >= 0; i--)
             if (ch[i].ref >= 0) stack.push_back(ch[i].ref);
     }
@@ -209,6 +153,7 @@ void number_wide(const int32_t* nodes, int64_t numNodes, std::vector<int32_t>& w
     std::vector<int32_t> tasks;                     // the binary roots of the subtree tasks
     std::vector<std::pair<int32_t, int>> stack{{0, 0}};
     Child ch[4];
+    bool bad = false;
     while (!stack.empty()) {
         const auto [ref, depth] = stack.back();
         stack.pop_back();
@@ -218,12 +163,12 @@ void number_wide(const int32_t* nodes, int64_t numNodes, std::vector<int32_t>& w
             continue;
         }
         top.push_back(ref);
-        const int n = collapse(nodes, ref, ch);
+        const int n = collapse(nodes, numNodes, ref, ch, &bad);
         for (int i = n - 1; i >= 0; i--)
             if (ch[i].ref >= 0) stack.push_back({ch[i].ref, depth + 1});
     }
     std::vector<std::vector<int32_t>> sub(tasks.size());
-    parallel_for((int64_t)tasks.size(), [&](int64_t i) { preorder(nodes, tasks[(size_t)i], sub[(size_t)i]); });
+    parallel_for((int64_t)tasks.size(), [&](int64_t i) { preorder(nodes, numNodes, tasks[(size_t)i], sub[(size_t)i]); });
     std::vector<int64_t> base(tasks.size(), 0);
     for (int32_t e : top) {
         if (e >= 0) {
@@ -275,9 +220,10 @@ bool build_wide4q(const int32_t* nodes, int64_t numNodes, std::vector<uint32_t>*
     std::atomic<bool> ok{true};
     parallel_for((int64_t)((order.size() + 4095) / 4096), [&](int64_t chunk) {
     Child ch[4];
+    bool bad = false;
     const size_t end = std::min(order.size(), (size_t)(chunk + 1) * 4096);
     for (size_t w = (size_t)chunk * 4096; w < end; w++) {
-        const int n = collapse(nodes, order[w], ch);
+        const int n = collapse(nodes, numNodes, order[w], ch, &bad);
         uint32_t* o = out->data() + w * 16;
         uint32_t exps = 0;
         for (int k = 0; k < 3; k++) {
@@ -305,7 +251,7 @@ bool build_wide4q(const int32_t* nodes, int64_t numNodes, std::vector<uint32_t>*
         o[3] = exps;
         for (int c = 0; c < 4; c++) {
             int32_t ref = kEntrypointSentinel;
-            if (c < n) ref = ch[c].ref >= 0 ? wideOf[(size_t)(ch[c].ref / 4)] * 4 : wide_leaf_ref(ch[c].ref, woopX, woopSlots);
+            if (c < n) ref = ch[c].ref >= 0 ? wideOf[(size_t)(ch[c].ref / 4)] * 4 : wide::wide_leaf_ref(ch[c].ref, woopX, 1, woopSlots);
             o[12 + c] = (uint32_t)ref;
         }
     }
@@ -327,30 +273,14 @@ std::vector<uint32_t> build_wide4(const int32_t* nodes, int64_t numNodes, const 
     if (srcMap) srcMap->assign(order.size() * 4, -1);
     parallel_for((int64_t)((order.size() + 4095) / 4096), [&](int64_t chunk) {
     Child ch[4];
+    bool bad = false;
     const size_t end = std::min(order.size(), (size_t)(chunk + 1) * 4096);
     for (size_t w = (size_t)chunk * 4096; w < end; w++) {
-        const int n = collapse(nodes, order[w], ch);
-        uint32_t* o = out.data() + w * 32;
-        for (int c = 0; c < 4; c++) {
-            const int f4 = c >> 1, pair = (c & 1) * 2;   // children 0,1 in float4 0/2/4, 2,3 in 1/3/5
-            // an absent child: NaN planes (every slab test of it fails) and the sentinel ref
-            const float qnan = std::numeric_limits<float>::quiet_NaN();
-            float lo[3] = {qnan, qnan, qnan}, hi[3] = {qnan, qnan, qnan};
-            int32_t ref = kEntrypointSentinel;
-            if (c < n) {
-                for (int k = 0; k < 3; k++) {
-                    lo[k] = ch[c].lo[k];
-                    hi[k] = ch[c].hi[k];
-                }
-                ref = ch[c].ref >= 0 ? wideOf[(size_t)(ch[c].ref / 4)] * 8 : wide_leaf_ref(ch[c].ref, woopX, woopSlots);
-            }
-            for (int k = 0; k < 3; k++) {
-                std::memcpy(&o[(2 * k + f4) * 4 + pair], &lo[k], 4);
-                std::memcpy(&o[(2 * k + f4) * 4 + pair + 1], &hi[k], 4);
-            }
-            o[6 * 4 + c] = (uint32_t)ref;
-            if (srcMap && c < n) (*srcMap)[w * 4 + c] = ch[c].src;
-        }
+        const int n = collapse(nodes, numNodes, order[w], ch, &bad);
+        int32_t refs[4] = {kEntrypointSentinel, kEntrypointSentinel, kEntrypointSentinel, kEntrypointSentinel};
+        for (int c = 0; c < n; c++)
+            refs[c] = ch[c].ref >= 0 ? wideOf[(size_t)(ch[c].ref / 4)] * 8 : wide::wide_leaf_ref(ch[c].ref, woopX, 1, woopSlots);
+        wide::wide_node_words(ch, n, refs, out.data() + w * 32, srcMap ? srcMap->data() + w * 4 : nullptr);
     }
     });
     return out;

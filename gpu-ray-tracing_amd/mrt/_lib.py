@@ -32,6 +32,7 @@ MRT_ERR_HIP = 3
 MRT_ERR_TOO_LARGE = 5
 MRT_ERR_STACK_OVERFLOW = 6
 MRT_LBVH_DEFAULT_MAX_LEAF = 4
+MRT_DERIVE_MAX_LEVELS = 1024
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -67,6 +68,12 @@ class BuildInfo(C.Structure):
     _fields_ = [("wall_ms", C.c_double), ("plan_ms", C.c_double), ("bind_ms", C.c_double), ("sort_ms", f32),
                 ("emit_ms", f32), ("fit_ms", f32), ("levels", i32), ("records", i64), ("leaves", i64), ("slots", i64),
                 ("scratch_bytes", i64), ("skipped_refs", i64), ("max_leaf_size", i32)]
+
+
+class DeriveInfo(C.Structure):
+    _fields_ = [("on_device_plan", i32), ("on_device_wide", i32), ("levels", i32), ("depth_levels", i32),
+                ("wide_nodes", i64), ("launches", i32), ("readbacks", i32), ("topo_ms", f32), ("collapse_ms", f32),
+                ("emit_ms", f32), ("wall_ms", C.c_double), ("scratch_bytes", i64)]
 
 
 class TunedSchedule(C.Structure):
@@ -114,6 +121,11 @@ TRACE_SYMBOLS = [
                                C.POINTER(i64), C.POINTER(i64), vp]),
     ("mrt_tracer_build_info", i32, [vp, C.POINTER(BuildInfo)]),
     ("mrt_tracer_copy_wide_nodes", i32, [vp, vp, i64, C.POINTER(i64)]),
+    ("mrt_tracer_bind_device", i32, [vp, vp, i64, vp, i64, vp, i64, vp]),
+    ("mrt_tracer_build_device", i32, [vp, vp, i64, vp, i64, C.POINTER(LbvhParams), vp, i64, vp, i64, vp, i64,
+                                      C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp]),
+    ("mrt_tracer_derive_info", i32, [vp, C.POINTER(DeriveInfo)]),
+    ("mrt_tracer_copy_refit_plan", i32, [vp, vp, vp, i32, C.POINTER(i32), vp, i64, C.POINTER(i64)]),
     ("mrt_refit_plan", i32, [vp, i64, vp, vp, i32, C.POINTER(i32), vp, i64, C.POINTER(i64)]),
     ("mrt_derive_wide_nodes", i32, [vp, i64, vp, i64, i32, vp, i64, C.POINTER(i64)]),
     ("mrt_bind_bvh", i32, [vp, i64, vp, i64, vp, i64]),

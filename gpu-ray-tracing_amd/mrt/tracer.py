@@ -181,11 +181,44 @@ class Tracer:
         _lib.check(self.lib.mrt_tracer_tune_import(self._h, arr, len(entries)))
 
     # -- CudaTracer API --------------------------------------------------------
-    def set_bvh(self, bvh: GpuBvh) -> None:
-        """setBVH + bind_CudaBVHTexture (CudaTracer.cc:142-146); re-binding is allowed."""
-        _lib.check(self.lib.mrt_tracer_bind(self._h, bvh.nodes.data_ptr(), bvh.node_bytes, bvh.woop.data_ptr(),
-                                            bvh.woop_bytes, bvh.tri_index.data_ptr(), bvh.tri_index_bytes))
+    def set_bvh(self, bvh: GpuBvh, on_device: bool = False, stream=None) -> None:
+        """setBVH + bind_CudaBVHTexture (CudaTracer.cc:142-146); re-binding is allowed.
+        on_device: derive the 4-wide array and the refit plan on the device, on `stream`
+        (mrt_tracer_bind_device: the same array; a tree that is none raises and leaves the
+        tracer unbound)."""
+        args = (self._h, bvh.nodes.data_ptr(), bvh.node_bytes, bvh.woop.data_ptr(), bvh.woop_bytes,
+                bvh.tri_index.data_ptr(), bvh.tri_index_bytes)
+        if on_device:
+            self.bvh = None
+            _lib.check(self.lib.mrt_tracer_bind_device(*args, _stream_ptr(stream)))
+        else:
+            _lib.check(self.lib.mrt_tracer_bind(*args))
         self.bvh = bvh
+
+    def derive_info(self) -> dict:
+        """The last device bind, device build or device-made refit plan: which parts were derived
+        on the device, levels, wide nodes, launches, readbacks, phase and wall ms, scratch bytes
+        (mrt_tracer_derive_info)."""
+        d = _lib.DeriveInfo()
+        _lib.check(self.lib.mrt_tracer_derive_info(self._h, C.byref(d)))
+        return {k: getattr(d, k) for k, _ in d._fields_}
+
+    def refit_plan(self):
+        """Blocking copy of the installed refit plan in mrt.tracer.refit_plan's shapes: (order,
+        level offsets, wide source map or None); None when no plan is installed."""
+        if self.bvh is None:
+            return None
+        levels, nsrc = C.c_int32(), C.c_int64()
+        _lib.check(self.lib.mrt_tracer_copy_refit_plan(self._h, None, None, 0, C.byref(levels), None, 0, C.byref(nsrc)))
+        if levels.value == 0:
+            return None
+        order = np.empty(self.bvh.node_bytes // 64, np.int32)
+        offsets = np.empty(levels.value + 1, np.int64)
+        src = np.empty(nsrc.value, np.int32)
+        _lib.check(self.lib.mrt_tracer_copy_refit_plan(self._h, order.ctypes.data, offsets.ctypes.data, len(offsets),
+                                                       C.byref(levels), src.ctypes.data if src.size else None,
+                                                       src.size, C.byref(nsrc)))
+        return order, offsets, (src if src.size else None)
 
     # -- refit (moving geometry, fixed topology) ---------------------------------
     def refit(self, vertices, triangles, stream=None) -> None:
@@ -216,31 +249,34 @@ class Tracer:
         return {k: getattr(r, k) for k, _ in r._fields_}
 
     # -- device build (new geometry, no host BVH) ---------------------------------
-    def build(self, vertices, triangles, max_leaf_size=None, stream=None) -> GpuBvh:
+    def build(self, vertices, triangles, max_leaf_size=None, stream=None, on_device: bool = False) -> GpuBvh:
         """Build a linear BVH of the triangles on the device and bind it (mrt_tracer_build):
         blocking. vertices float32 [nv, 3], triangles int32 [nt, 3] as device tensors; numpy
         arrays are uploaded. Returns the bound GpuBvh, its tensors trimmed to the bytes written
         (views of buffers sized by mrt_lbvh_sizes). max_leaf_size 1..8 (None = the default).
         Faster than mrt.Bvh.build + upload by orders of magnitude, slower to trace (no SAH, no
-        spatial splits): for new or re-meshed geometry; Tracer.refit covers moved vertices."""
+        spatial splits): for new or re-meshed geometry; Tracer.refit covers moved vertices.
+        on_device: the level plan and the bind's 4-wide array are derived on the device too
+        (mrt_tracer_build_device: the same bytes, no node array crosses to the host)."""
         dev = torch.device("cuda", self.device)
 
-        def on_device(a, dtype, np_dtype):
+        def to_device(a, dtype, np_dtype):
             if isinstance(a, torch.Tensor):
                 return a.to(dev, dtype).contiguous().view(-1, 3)
             a = np.ascontiguousarray(a, np_dtype).reshape(-1, 3)
             return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-        v = on_device(vertices, torch.float32, np.float32)
-        t = on_device(triangles, torch.int32, np.int32)
+        v = to_device(vertices, torch.float32, np.float32)
+        t = to_device(triangles, torch.int32, np.int32)
         cap = [C.c_int64(), C.c_int64(), C.c_int64()]
         _lib.check(self.lib.mrt_lbvh_sizes(t.shape[0], *map(C.byref, cap)))
         nodes, woop, tri = (torch.empty(c.value // 4, dtype=torch.int32, device=dev) for c in cap)
         params = _lib.LbvhParams(max_leaf_size=int(max_leaf_size or 0))
         out = [C.c_int64(), C.c_int64(), C.c_int64()]
-        _lib.check(self.lib.mrt_tracer_build(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0],
-                                             C.byref(params), nodes.data_ptr(), cap[0].value, woop.data_ptr(),
-                                             cap[1].value, tri.data_ptr(), cap[2].value, *map(C.byref, out),
-                                             _stream_ptr(stream)))
+        fn = self.lib.mrt_tracer_build_device if on_device else self.lib.mrt_tracer_build
+        _lib.check(fn(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0],
+                      C.byref(params), nodes.data_ptr(), cap[0].value, woop.data_ptr(),
+                      cap[1].value, tri.data_ptr(), cap[2].value, *map(C.byref, out),
+                      _stream_ptr(stream)))
         bvh = GpuBvh.__new__(GpuBvh)
         bvh.nodes, bvh.woop, bvh.tri_index = (a[:o.value // 4] for a, o in zip((nodes, woop, tri), out))
         bvh.device = dev

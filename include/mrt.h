@@ -348,8 +348,10 @@ int  mrt_tracer_last_kernel_key(const mrt_tracer* t);
  *     box, and is counted (mrt_refit_info.skipped_refs). Nothing is reported here.
  *   - Ordering: stream-ordered on `stream` (a hipStream_t, NULL = the null stream) without a
  *     host sync, after the first refit following a bind or set_config, which builds the
- *     refit plan (one synchronous copy of the nodes to the host; mrt_refit_info.plan_bytes
- *     on the device until the next bind, unbind or set_config). The refit runs after this
+ *     refit plan (synchronous; on the device, mrt_tracer_bind_device below, or from one copy
+ *     of the nodes to the host for a tree of more than MRT_DERIVE_MAX_LEVELS depth levels;
+ *     mrt_refit_info.plan_bytes on the device until the next bind, unbind or set_config).
+ *     After mrt_tracer_bind_device / mrt_tracer_build_device the plan is already there. The refit runs after this
  *     handle's traces enqueued on `stream` before it, and traces enqueued on `stream` after
  *     it see the refitted tree. A trace on ANOTHER stream that overlaps a refit reads a
  *     half-updated tree: ordering those (events, synchronisation) is the caller's job.
@@ -373,7 +375,8 @@ int  mrt_tracer_refit(mrt_tracer* t, const float* vertices, int64_t numVertices,
 
 /* Blocking (waits for the device): the plan's levels and bytes, the last refit's launches,
  * and the out-of-range references skipped since the previous call (reset by it). All zero
- * before the first refit after a bind / set_config. */
+ * before the first refit after a bind / set_config (a device bind or build installs the plan:
+ * levels and plan_bytes are reported at once). */
 int  mrt_tracer_refit_info(mrt_tracer* t, mrt_refit_info* info);
 
 /* Blocking debug copy-out of the derived 4-wide array (device -> host), e.g. after a
@@ -452,6 +455,72 @@ int  mrt_tracer_build(mrt_tracer* t, const float* vertices, int64_t numVertices,
 
 /* The last successful mrt_tracer_build of this handle (all zero before one). */
 int  mrt_tracer_build_info(mrt_tracer* t, mrt_build_info* info);
+
+/* ---- the refit plan and the 4-wide array derived on the device -------------------------- */
+/* A tree of more depth levels than this is derived on the host instead (every pass of the
+ * device derivation is one launch per depth level, or per run of small levels). */
+enum { MRT_DERIVE_MAX_LEVELS = 1024 };
+
+/* What mrt_tracer_derive_info reports about the last mrt_tracer_bind_device, mrt_tracer_build_device
+ * or device-made refit plan of this handle (all zero before one). */
+typedef struct mrt_derive_info {
+    int32_t on_device_plan;    /* 1: the refit plan (height levels) was derived on the device; 0: on the
+                                  host (a tree of more than MRT_DERIVE_MAX_LEVELS depth levels)          */
+    int32_t on_device_wide;    /* 1: the 4-wide array and its source map were; 0: on the host (cfg.wide 2,
+                                  the host fallback above) or none was derived (cfg.wide 0, a stack bound
+                                  above 1024 entries)                                                    */
+    int32_t levels;            /* height levels (mrt_refit_info.levels)                                  */
+    int32_t depth_levels;      /* depth levels: the launches of a pass are at most this many             */
+    int64_t wide_nodes;        /* 128-byte wide nodes written on the device                              */
+    int32_t launches;          /* kernel launches of the derivation (the sort counts as one)             */
+    int32_t readbacks;         /* host waits for a copy from the device: one fixed-size summary per
+                                  topology launch, then a few summaries and 4 bytes per level             */
+    float   topo_ms;           /* device (events): topology, heights, the sort                           */
+    float   collapse_ms;       /* device: wide roots, sizes, numbers and the stack bound                 */
+    float   emit_ms;           /* device: the wide nodes and the source map                              */
+    double  wall_ms;           /* host wall time of the derivation (of the whole bind in a bind)         */
+    int64_t scratch_bytes;     /* stream-ordered scratch taken and returned (48 bytes per node and the sort's)    */
+} mrt_derive_info;
+
+/* mrt_tracer_bind with the derived data made on the device: the same argument checks and effects
+ * (the autotuner's schedules and the refit plan are forgotten), but no node array crosses to the
+ * host. The launches run on `stream` (a hipStream_t, NULL = the null stream); the call returns
+ * after the device has finished (the wide array's size is read back to allocate it).
+ *   - The refit plan is derived and installed in every case, so the first mrt_tracer_refit copies
+ *     nothing to the host and mrt_tracer_refit_info reports the levels at once.
+ *   - cfg.wide 1: the exact 4-wide array, its source map and stack bound, byte for byte what
+ *     mrt_tracer_bind derives (one collapse arithmetic, csrc/wide_common.hpp). cfg.wide 0: the
+ *     plan only. cfg.wide 2: the plan on the device, the quantized array through
+ *     mrt_tracer_bind's host path (mrt_derive_info.on_device_wide 0). A stack bound above 1024
+ *     entries keeps the binary traversal, as mrt_tracer_bind does.
+ *   - Every ref is checked on the device before it is followed. A tree that is none (a child ref
+ *     outside the array or not a record's first float4, a record reached twice, a cycle, a record
+ *     not reachable from node 0) is MRT_ERR_INVALID_ARG with mrt_refit_plan's reason, and the
+ *     tracer is left UNBOUND.
+ *   - More than MRT_DERIVE_MAX_LEVELS depth levels: everything through mrt_tracer_bind's host
+ *     path (mrt_derive_info.on_device_plan 0). */
+int  mrt_tracer_bind_device(mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
+                            const int32_t* triIndex, int64_t triIndexBytes, void* stream);
+
+/* mrt_tracer_build (same arguments, checks, outputs and bytes written) with the level plan and the
+ * bind's derived data made on the device: topology pass on the emitted nodes, the refit launches
+ * with that plan, the collapse and emission, the bind, the plan kept for later refits. Still
+ * blocking (the byte counts are return values), but no node array crosses to the host.
+ * mrt_build_info.plan_ms and bind_ms are the host wall time of those phases. */
+int  mrt_tracer_build_device(mrt_tracer* t, const float* vertices, int64_t numVertices, const int32_t* triangles,
+                             int64_t numTriangles, const mrt_build_params* params, void* nodes, int64_t nodeCapacity,
+                             void* woop, int64_t woopCapacity, int32_t* triIndex, int64_t triIndexCapacity,
+                             int64_t* nodeBytes, int64_t* woopBytes, int64_t* triIndexBytes, void* stream);
+
+int  mrt_tracer_derive_info(mrt_tracer* t, mrt_derive_info* info);
+
+/* Blocking copy-out of the installed refit plan (device -> host), for tests and tools, in
+ * mrt_refit_plan's shapes: order (nodeBytes / 64 entries, may be NULL), levelOffsets
+ * (*numLevels + 1 entries; levelCapacity = entries it holds, MRT_ERR_TOO_LARGE when too few; may
+ * be NULL), wideSrc (may be NULL; *numWideSrc entries, 0 without an exact wide array).
+ * *numLevels = 0 when no plan is installed (before the first refit after a host bind). */
+int  mrt_tracer_copy_refit_plan(mrt_tracer* t, int32_t* order, int64_t* levelOffsets, int32_t levelCapacity,
+                                int32_t* numLevels, int32_t* wideSrc, int64_t wideSrcCapacity, int64_t* numWideSrc);
 
 /* Host-only (no device): the refit plan of a Compact2 node array (host memory), as the
  * tracer builds it (csrc/refit_plan.cpp). order (nodeBytes / 64 entries, may be NULL): every
