@@ -86,11 +86,14 @@ int mrth_scene_copy_arrays(const mrth_scene* s, float* vertices, int32_t* triang
 
 namespace {
 // Vec4f::toABGR, host variant (reference Math.cc:45-52): clamp, scale by 2^56 in
-// double, times 255, round half up in fixed point.
+// double, times 255, round half up in fixed point. The clamp is the framework's
+// min(max(v, 0), 1) with max(a, b) = a > b ? a : b (Defs.hh:141-159), which sends a NaN
+// channel (the shade of a triangle whose normal overflowed) to 0, not through.
 uint32_t host_to_abgr(const float v[4]) {
     uint32_t r = 0;
     for (int i = 0; i < 4; i++) {
-        const float c = v[i] < 0.0f ? 0.0f : (v[i] > 1.0f ? 1.0f : v[i]);
+        const float lo = v[i] > 0.0f ? v[i] : 0.0f;
+        const float c = lo < 1.0f ? lo : 1.0f;
         const uint64_t q = (uint64_t)((double)c * 72057594037927936.0);   // exp2(56)
         r |= (uint32_t)((((q * 255u) >> 55) + 1) >> 1) << (8 * i);
     }

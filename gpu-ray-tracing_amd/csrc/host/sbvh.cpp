@@ -522,19 +522,24 @@ private:
     std::atomic<int> freeThreads_{0};
 };
 
-void collect_stats(const BvhNode& n, int depth, float rootArea, const BuildParams& p, BvhStats& s) {
+// BVH::BVH's statistics (reference BVH.cc:48-61): the SAH cost as
+// BVHNode::computeSubtreeProbabilities accumulates it (BVHNode.cc:66-81), in preorder, each
+// child's probability chained from its parent's as prob * childArea / parentArea (so its
+// rounding is the reference's, not that of area / rootArea).
+void collect_stats(const BvhNode& n, int depth, float prob, const BuildParams& p, BvhStats& s) {
     s.maxDepth = std::max<int64_t>(s.maxDepth, depth);
-    const float prob = rootArea > 0.0f ? n.bounds.area() / rootArea : 0.0f;
     if (n.is_leaf()) {
         s.leafNodes++;
         s.triRefs += (int64_t)n.tris.size();
-        s.sahCost += prob * (float)n.tris.size() * p.sahTriangleCost;
+        s.sahCost += prob * (0.0f * p.sahNodeCost + (float)n.tris.size() * p.sahTriangleCost);
         return;
     }
     s.innerNodes++;
-    s.sahCost += prob * 2.0f * p.sahNodeCost;
-    collect_stats(*n.child[0], depth + 1, rootArea, p, s);
-    collect_stats(*n.child[1], depth + 1, rootArea, p, s);
+    s.sahCost += prob * (2.0f * p.sahNodeCost + 0.0f * p.sahTriangleCost);
+    for (int i = 0; i < 2; i++) {
+        const float childProb = prob > 0.0f ? prob * n.child[i]->bounds.area() / n.bounds.area() : 0.0f;
+        collect_stats(*n.child[i], depth + 1, childProb, p, s);
+    }
 }
 
 }  // namespace
@@ -545,7 +550,7 @@ std::unique_ptr<BvhNode> build_sbvh(const Scene& scene, const BuildParams& param
     std::unique_ptr<BvhNode> root = b.run();
     if (stats) {
         *stats = BvhStats();
-        collect_stats(*root, 0, root->bounds.area(), params, *stats);
+        collect_stats(*root, 0, 1.0f, params, *stats);
         stats->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     return root;

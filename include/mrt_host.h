@@ -55,6 +55,13 @@ typedef struct mrth_bvh_stats {
  * triangle counts; "hairball" with param > 0: that many tubes, unpadded), "sphere" (param = rings), "random" (param = triangles). */
 int  mrth_scene_synthetic(const char* name, int64_t param, uint64_t seed, mrth_scene** out);
 int  mrth_scene_load_obj(const char* path, mrth_scene** out);
+/* Positions and indices taken as they are; the default material. The same mesh written as an .obj and
+ * read by mrth_scene_load_obj is another scene to mrth_scene_hash (and so another bvhcache name) for
+ * two reasons, and only these (tests/test_ref_host.py): the reference's importer parses decimals by
+ * accumulating in float32 (String.cc:452-509), so the text of a float32 comes back up to a few ulps
+ * off unless it is a short dyadic number, and it numbers vertices in order of first use by a face
+ * (MeshWavefrontIO.cc:317-348), without welding equal positions. from_arrays of load_obj's own
+ * positions and indices (mrth_scene_copy_arrays) hashes like load_obj. */
 int  mrth_scene_from_arrays(const float* vertices, int64_t numVertices, const int32_t* triangles,
                             int64_t numTriangles, mrth_scene** out);
 void mrth_scene_destroy(mrth_scene* s);

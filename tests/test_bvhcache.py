@@ -4,9 +4,8 @@ buildParams.computeHash(), BVHLayout_Compact2). The framework hash
 (src/framework/base/Hash.hh:181-201, Hash.cc:34-112) is restated independently
 here and compared with the host library's.
 
-Parity unpinned against the reference binary: its Hash.cc cannot be compiled here
-(Defs.hh:188-190 includes <cuda.h> unconditionally, absent from this image), so the
-pins are this restatement and the hand-derived values below.
+The reference's own compiled Hash.cc, Scene.cc and importer judge the same functions in
+tests/test_ref_host.py; this restatement and the hand-derived values below stand beside it.
 """
 import ctypes as C
 import os
