@@ -207,7 +207,7 @@ int derive_report(mrt_tracer* t, const DeriveRun& r, bool plan, bool wide, doubl
 }
 
 int bind_derived(mrt_tracer* t, DeriveRun& r, RefitPlan&& p, const void* nodes, int64_t nodeBytes, const void* woop,
-                 int64_t woopBytes, const int32_t* triIndex, int64_t triIndexBytes, hipStream_t s) {
+                 int64_t woopBytes, const int32_t* triIndex, int64_t triIndexBytes, hipStream_t s, bool keepTunes) {
     const auto t0 = std::chrono::steady_clock::now();
     t->nodes = nodes;
     t->nodeBytes = nodeBytes;
@@ -216,7 +216,7 @@ int bind_derived(mrt_tracer* t, DeriveRun& r, RefitPlan&& p, const void* nodes, 
     t->triIndex = triIndex;
     t->triIndexBytes = triIndexBytes;
     t->bound = true;
-    tune_reset(t);
+    if (!keepTunes) tune_reset(t);
     drop_plan(t);
     // launches in flight may still read the old wide array: wait for this handle's own
     if (int rc = wait_all_workspaces(t)) return rc;

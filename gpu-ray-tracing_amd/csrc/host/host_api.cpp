@@ -1,4 +1,5 @@
 // host_api.cpp — the C-ABI of include/mrt_host.h over the host C++ pieces.
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -11,6 +12,9 @@
 #include "fwhash.hpp"
 #include "raygen.hpp"
 #include "scene.hpp"
+#include "treelet.hpp"
+
+static_assert(MRTH_OPTIMIZE_MAX_ROUNDS == mrt::kOptimizeMaxRounds, "mrt_host.h and treelet.hpp disagree");
 
 struct mrth_scene {
     mrt::Scene scene;
@@ -296,6 +300,26 @@ int mrth_bvh_refit(mrth_bvh* b, const float* vertices, int64_t numVertices, cons
     std::string err;
     if (!mrt::refit_compact2(b->c2, vertices, numVertices, triangles, numTriangles, &err))
         return fail(MRTH_ERR_INVALID_ARG, err);
+    return MRTH_OK;
+}
+
+int mrth_bvh_optimize(mrth_bvh* b, int32_t rounds, mrth_optimize_info* info) {
+    if (!b) return fail(MRTH_ERR_INVALID_ARG, "null bvh");
+    if (rounds < 0 || rounds > MRTH_OPTIMIZE_MAX_ROUNDS) return fail(MRTH_ERR_INVALID_ARG, "optimize: rounds outside 0..8");
+    const auto t0 = std::chrono::steady_clock::now();
+    mrt::OptimizeStats st;
+    if (const char* why = mrt::optimize_nodes(b->c2.nodes.data(), (int64_t)b->c2.nodes.size() / 16, rounds ? rounds : 1, &st))
+        return fail(MRTH_ERR_INVALID_ARG, std::string("optimize: the nodes are not a tree: ") + why);
+    if (info) {
+        *info = mrth_optimize_info{};
+        info->rounds = st.rounds;
+        info->levels = st.levels;
+        for (int r = 0; r < MRTH_OPTIMIZE_MAX_ROUNDS; r++) {
+            info->considered[r] = st.considered[r];
+            info->rewritten[r] = st.rewritten[r];
+        }
+        info->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
     return MRTH_OK;
 }
 

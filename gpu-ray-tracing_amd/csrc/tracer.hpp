@@ -3,7 +3,7 @@
 // works on its own: the handle's lifecycle, configuration, workspace pool, tune events and the
 // trace path (mrt_api.cpp), bind and the 4-wide derivation (bind_api.cpp), refit (refit_api.cpp),
 // the device build (build_api.cpp), the plan and the 4-wide array derived on the device
-// (derive_api.cpp).
+// (derive_api.cpp), the treelet restructuring (optimize_api.cpp).
 #pragma once
 #include <chrono>
 #include <cstdint>
@@ -126,6 +126,7 @@ struct mrt_tracer {
     mrt::RefitPlan plan;
     mrt_build_info lastBuild{};        // the last successful mrt_tracer_build (mrt_tracer_build_info)
     mrt_derive_info lastDerive{};      // the last device bind / build / plan (mrt_tracer_derive_info)
+    mrt_optimize_info lastOptimize{};  // the last successful mrt_tracer_optimize (mrt_tracer_optimize_info)
 
     // Launch scratch, one set per stream the handle has launched on: the stack
     // spill slab, the queue heads and the overflow counter are written by a
@@ -181,12 +182,13 @@ int enqueue_refit(const RefitArgs& a, const std::vector<int64_t>& levelOffsets, 
 // offsets, levels, valid, skipped; not wideSrc, not built) and sets *status: kDeriveMalformed
 // with *why = refit_levels' reason, kDeriveTooDeep above MRT_DERIVE_MAX_LEVELS depth levels (the
 // caller takes the host path). bind_derived is bind_locked for a tree whose plan p was derived
-// by r: the bookkeeping, the wide array per cfg.wide, the plan installed. All enqueue on s;
+// by r: the bookkeeping, the wide array per cfg.wide, the plan installed (keepTunes: the same
+// buffers re-installed by optimize_api.cpp, the tuned schedules stay). All enqueue on s;
 // bind_derived returns after the device has finished. derive_report fills t->lastDerive.
 int derive_begin(DeriveRun& r, const void* nodes, int64_t numNodes, hipStream_t s);
 int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, int* status, const char** why);
 int bind_derived(mrt_tracer* t, DeriveRun& r, RefitPlan&& p, const void* nodes, int64_t nodeBytes, const void* woop,
-                 int64_t woopBytes, const int32_t* triIndex, int64_t triIndexBytes, hipStream_t s);
+                 int64_t woopBytes, const int32_t* triIndex, int64_t triIndexBytes, hipStream_t s, bool keepTunes = false);
 int derive_report(mrt_tracer* t, const DeriveRun& r, bool plan, bool wide, double wallMs);
 // The source map a refit of the exact wide array reads: the plan's copy or the wide array's own.
 const int32_t* refit_wide_src(const mrt_tracer* t);

@@ -76,6 +76,20 @@ class DeriveInfo(C.Structure):
                 ("emit_ms", f32), ("wall_ms", C.c_double), ("scratch_bytes", i64)]
 
 
+class HostOptimizeInfo(C.Structure):
+    _fields_ = [("rounds", i32), ("levels", i32), ("considered", i64 * 8), ("rewritten", i64 * 8),
+                ("wall_ms", C.c_double)]
+
+
+class OptimizeParams(C.Structure):
+    _fields_ = [("rounds", i32)]
+
+
+class OptimizeInfo(C.Structure):
+    _fields_ = [("rounds", i32), ("levels", i32), ("launches", i32), ("considered", i64 * 8), ("rewritten", i64 * 8),
+                ("device_ms", f32), ("wall_ms", C.c_double), ("scratch_bytes", i64)]
+
+
 class TunedSchedule(C.Structure):
     _fields_ = [("num_rays", i32), ("variant", i32), ("candidate", i32), ("version", i32)]
 
@@ -116,6 +130,8 @@ TRACE_SYMBOLS = [
     ("mrt_tracer_last_kernel_key", C.c_int, [vp]),
     ("mrt_tracer_refit", i32, [vp, vp, i64, vp, i64, vp]),
     ("mrt_tracer_refit_info", i32, [vp, C.POINTER(RefitInfo)]),
+    ("mrt_tracer_optimize", i32, [vp, C.POINTER(OptimizeParams), vp]),
+    ("mrt_tracer_optimize_info", i32, [vp, C.POINTER(OptimizeInfo)]),
     ("mrt_lbvh_sizes", i32, [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
     ("mrt_tracer_build", i32, [vp, vp, i64, vp, i64, C.POINTER(LbvhParams), vp, i64, vp, i64, vp, i64, C.POINTER(i64),
                                C.POINTER(i64), C.POINTER(i64), vp]),
@@ -179,6 +195,7 @@ HOST_SYMBOLS = [
                                C.POINTER(vp), C.POINTER(i64)]),
     ("mrth_bvh_get_stats", i32, [vp, C.POINTER(BvhStats)]),
     ("mrth_bvh_refit", i32, [vp, vp, i64, vp, i64]),
+    ("mrth_bvh_optimize", i32, [vp, i32, C.POINTER(HostOptimizeInfo)]),
     ("mrth_woopify", None, [C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
     ("mrth_pixel_table", i32, [i32, i32, vp]),
     ("mrth_primary_rays", i32, [C.POINTER(HostCamera), i32, i32, vp, vp]),

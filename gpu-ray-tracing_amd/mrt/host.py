@@ -233,6 +233,17 @@ class Bvh:
         t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
         _lib.check_host(_lib.host_lib().mrth_bvh_refit(self._h, _ptr(v), len(v), _ptr(t), len(t)))
 
+    def optimize(self, rounds: int = 1) -> dict:
+        """Re-optimise the topology in place by treelet restructuring (mrth_bvh_optimize): rounds
+        passes (1..8) over the height levels, below every record the 7-leaf treelet rebuilt as
+        the topology of smallest inner-box area when that is strictly smaller. Leaves, Woop rows
+        and triIndex stay. The CPU statement of Tracer.optimize, whose bytes it reproduces.
+        Returns rounds, levels, and per round the treelets considered and rewritten, wall ms."""
+        info = _lib.HostOptimizeInfo()
+        _lib.check_host(_lib.host_lib().mrth_bvh_optimize(self._h, int(rounds), C.byref(info)))
+        return {"rounds": info.rounds, "levels": info.levels, "considered": list(info.considered[:info.rounds]),
+                "rewritten": list(info.rewritten[:info.rounds]), "wall_ms": info.wall_ms}
+
     def stats(self) -> dict:
         s = _lib.BvhStats()
         _lib.check_host(_lib.host_lib().mrth_bvh_get_stats(self._h, C.byref(s)))

@@ -248,6 +248,25 @@ class Tracer:
         _lib.check(self.lib.mrt_tracer_refit_info(self._h, C.byref(r)))
         return {k: getattr(r, k) for k, _ in r._fields_}
 
+    # -- re-optimise (treelet restructuring) ---------------------------------------
+    def optimize(self, rounds: int = 1, stream=None) -> dict:
+        """Re-optimise the bound BVH's topology in place on the device by treelet restructuring
+        (mrt_tracer_optimize): blocking. rounds passes (1..8); after the last one the refit plan
+        and the 4-wide array are derived again on the device and installed, the settled schedules
+        stay. Writes the bound GpuBvh's nodes tensor, the bytes Bvh.optimize writes. Returns
+        mrt_tracer_optimize_info: rounds, levels, launches, per round the treelets considered
+        and rewritten, device and wall ms, scratch bytes."""
+        if self.bvh is None:
+            raise _lib.MrtError("Tracer: No BVH!")
+        params = _lib.OptimizeParams(rounds=int(rounds))
+        _lib.check(self.lib.mrt_tracer_optimize(self._h, C.byref(params), _stream_ptr(stream)))
+        o = _lib.OptimizeInfo()
+        _lib.check(self.lib.mrt_tracer_optimize_info(self._h, C.byref(o)))
+        out = {k: getattr(o, k) for k, _ in o._fields_}
+        out["considered"] = list(o.considered[:o.rounds])
+        out["rewritten"] = list(o.rewritten[:o.rounds])
+        return out
+
     # -- device build (new geometry, no host BVH) ---------------------------------
     def build(self, vertices, triangles, max_leaf_size=None, stream=None, on_device: bool = False) -> GpuBvh:
         """Build a linear BVH of the triangles on the device and bind it (mrt_tracer_build):

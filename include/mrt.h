@@ -342,7 +342,10 @@ int  mrt_tracer_last_kernel_key(const mrt_tracer* t);
  *   - Limits: a leaf box covers the whole triangle also where the SBVH builder had clipped
  *     the reference to a spatial split, so refitted boxes are correct but may be looser than
  *     built ones (traces get slower, never wrong); the tree is not re-optimised, so large
- *     deformations degrade it — rebuild (mrth_bvh_build + bind) when that shows.
+ *     deformations degrade it. When that shows, rebuild on the device (mrt_tracer_build_device:
+ *     1.65 ms for bunny) or, where the leaves must stay, restructure (mrt_tracer_optimize below:
+ *     bunny displaced by 10 % of its size traced 0.93x after one round, 0.85x after three,
+ *     0.77x after the rebuild); mrth_bvh_build + bind is the 20 s host route.
  *   - A triIndex entry outside [0, numTriangles) or a vertex index outside [0, numVertices)
  *     is never dereferenced: that triangle keeps its old rows, is left out of its leaf's
  *     box, and is counted (mrt_refit_info.skipped_refs). Nothing is reported here.
@@ -432,7 +435,10 @@ int  mrt_lbvh_sizes(int64_t numTriangles, int64_t* nodeBytes, int64_t* woopBytes
  *     first child's box. Boxes and Woop rows are what mrt_tracer_refit computes; the bytes
  *     equal mrth_bvh_build_lbvh's (mrt_host.h) and do not vary between runs.
  *   - Limits: the quality is below the SBVH's (no spatial splits, no SAH): traces are slower
- *     than on a mrth_bvh_build tree (DESIGN §10 has the measured ratio). Coincident centres
+ *     than on a mrth_bvh_build tree (DESIGN §10 has the measured ratio). mrt_tracer_optimize
+ *     below lowers the built tree's inner-area sum by 11-12 % per round-1 call, but the primary
+ *     trace followed only on hairball (0.99x after 1 round, 0.95x after 2) and not on bunny
+ *     (1.01-1.09x); DESIGN §11 has the run. Coincident centres
  *     split by index bits, so the depth can exceed 63: the per-lane binary order
  *     (MRT_TRACE_LOCKSTEP_OFF, cfg.wide 0) then reports MRT_ERR_STACK_OVERFLOW as for any deep
  *     tree, while the wide orders size their stack at bind.
@@ -535,6 +541,74 @@ int  mrt_tracer_copy_refit_plan(mrt_tracer* t, int32_t* order, int64_t* levelOff
  * array, a record reached twice or a record not reachable from node 0. */
 int  mrt_refit_plan(const void* nodes, int64_t nodeBytes, int32_t* order, int64_t* levelOffsets, int32_t levelCapacity,
                     int32_t* numLevels, int32_t* wideSrc, int64_t wideSrcCapacity, int64_t* numWideSrc);
+
+/* ---- re-optimising the bound tree on the device (treelet restructuring) ----------------- */
+enum { MRT_OPTIMIZE_MAX_ROUNDS = 8 };
+
+/* Parameters of mrt_tracer_optimize (NULL = defaults). */
+typedef struct mrt_optimize_params {
+    int32_t rounds;            /* passes over the tree: 1..MRT_OPTIMIZE_MAX_ROUNDS; 0 = default (1)        */
+} mrt_optimize_params;
+
+/* What mrt_tracer_optimize_info reports about the last successful mrt_tracer_optimize. */
+typedef struct mrt_optimize_info {
+    int32_t rounds;            /* passes run                                                             */
+    int32_t levels;            /* height levels of the tree as installed (mrt_refit_info.levels)         */
+    int32_t launches;          /* restructuring launches of all passes: one per level above 64 records,
+                                  one for the run of smaller levels (the derivations' are in
+                                  mrt_derive_info)                                                       */
+    int64_t considered[MRT_OPTIMIZE_MAX_ROUNDS];   /* per pass: records of height >= 1, one treelet each  */
+    int64_t rewritten[MRT_OPTIMIZE_MAX_ROUNDS];    /* per pass: treelets whose records were rewritten     */
+    float   device_ms;         /* device (events): the restructuring launches of all passes              */
+    double  wall_ms;           /* host wall time of the whole call, derivations and install included     */
+    int64_t scratch_bytes;     /* stream-ordered scratch of one derivation (mrt_derive_info.scratch_bytes)
+                                  + the counters' 32 bytes                                               */
+} mrt_optimize_info;
+
+/* Re-optimise the topology of the bound Compact2 tree in place, on the device, by treelet
+ * restructuring (Karras & Aila 2013; no reference counterpart): the cure for a device-built
+ * tree's quality and for a tree that refits have degraded, without a host rebuild. The bound
+ * nodes buffer must be writable, as for mrt_tracer_refit; woop and triIndex are not touched.
+ *   - A pass derives the height levels on the device (as mrt_tracer_bind_device does, which
+ *     also checks that the nodes are a tree) and then, level by level from height 1 up, forms
+ *     below every record a treelet of at most 7 leaves, finds by exact dynamic programming over
+ *     its 128 leaf subsets the binary topology of smallest summed inner-box area, and rewrites
+ *     the treelet's records when that sum is strictly below the present one. Every rule and
+ *     tie is csrc/treelet_common.hpp's; the bytes equal mrth_bvh_optimize's (mrt_host.h, which
+ *     states what stays and which treelets are skipped) and do not vary between runs. One wave
+ *     per treelet; one launch per level, one workgroup for the run of small levels; records of
+ *     one level have disjoint subtrees, so no workgroup reads what another wrote in a launch.
+ *   - After the last pass the refit plan, the exact 4-wide array, its source map and the
+ *     stack bound are derived and installed exactly as mrt_tracer_bind_device does on the same
+ *     buffers (cfg.wide 0 and 2 as there; mrt_derive_info describes it), so the next refit
+ *     and trace work with no further step. Kept: the bind and the autotuner's schedules
+ *     (the batches and kernels are the same; a trace's time on the new tree differs, and a
+ *     caller may re-tune with mrt_tracer_set_config). Workspaces grow with the next trace if
+ *     the stack bound grew (mrt_bind_info.stack_capacity). A tree that has MORE than
+ *     MRT_DERIVE_MAX_LEVELS depth levels after a pass (none observed: passes shorten trees)
+ *     ends the passes there and is installed through mrt_tracer_bind's host path, which
+ *     forgets the schedules.
+ *   - BLOCKING, like mrt_tracer_bind_device: the launches run on `stream` (a hipStream_t, NULL
+ *     = the null stream) and the call returns after the device has finished. It first waits
+ *     for this handle's own launches; a trace or refit of ANOTHER handle or a raw kernel that
+ *     overlaps it on another stream reads a half-written tree: ordering those is the caller's.
+ *   - What it buys is measured, not promised (tools/optimize_probe.py): one round
+ *     takes 3.8 ms on bunny (50 664 records) and 21 ms on hairball (2.4 M), 1.7 and 15 ms of
+ *     it on the device, and lowers the inner-area sum of a fresh LBVH to 0.89 / 0.88. The
+ *     1024x768 primary trace on that tree went to 1.01x (bunny) and 0.99x (hairball) of the
+ *     un-optimized LBVH's, 2 and 3 rounds to 1.09x / 1.05x and 0.95x / 0.96x: within the
+ *     spread between settled schedules on bunny, so the default stays 1 round. On bunny
+ *     refitted to vertices displaced by 10 % of its size: 0.93x after 1 round, 0.85x after 3;
+ *     a fresh mrt_tracer_build_device of the moved vertices took 1.65 ms and gave 0.77x.
+ * MRT_ERR_NOT_BOUND before a bind; MRT_ERR_INVALID_ARG for rounds outside 0..8 or bound nodes
+ * that are not a tree; MRT_ERR_TOO_LARGE for a bound tree of more than MRT_DERIVE_MAX_LEVELS
+ * depth levels (rebuild it, or optimise it with mrth_bvh_optimize and bind again). In all
+ * these cases no byte of the tree is written and the bind, its derived data and the
+ * schedules stand. */
+int  mrt_tracer_optimize(mrt_tracer* t, const mrt_optimize_params* params, void* stream);
+
+/* The last successful mrt_tracer_optimize of this handle (all zero before one). */
+int  mrt_tracer_optimize_info(mrt_tracer* t, mrt_optimize_info* info);
 
 /* Host-only (no device): the 4-wide node array a tracer derives at bind time
  * from a Compact2 node array (host memory). form 1 = exact child boxes, 128 B per

@@ -122,6 +122,34 @@ int  mrth_bvh_get_stats(const mrth_bvh* b, mrth_bvh_stats* out);
  * MRTH_ERR_INVALID_ARG and nothing is written. */
 int  mrth_bvh_refit(mrth_bvh* b, const float* vertices, int64_t numVertices, const int32_t* triangles,
                     int64_t numTriangles);
+/* Re-optimise the topology in place by treelet restructuring (Karras & Aila 2013; no reference
+ * counterpart; the CPU statement of mrt_tracer_optimize, mrt.h, whose bytes it reproduces).
+ * rounds 1..MRTH_OPTIMIZE_MAX_ROUNDS passes (0 = the default, 1). A pass takes the height levels
+ * of the tree as it stands (mrt_refit_plan's) and, level by level from height 1 up, forms below
+ * every record a treelet of at most 7 leaves (the two child slots, then repeatedly the inner leaf
+ * of largest float32 area dx*dy + dy*dz + dz*dx replaced by its two children, a tie to the earliest),
+ * finds by exact dynamic programming over the leaf subsets the binary topology with the smallest
+ * sum of inner-box areas, and rewrites the treelet's records when that sum is strictly below the
+ * present one (csrc/treelet_common.hpp states every tie rule). Leaves are not regrouped: the
+ * multiset of (leaf ref, leaf box) stays, as do the record count, words 14-15, Woop rows,
+ * triIndex and terminators. A rewritten inner box is the union of its record's two boxes, so a
+ * tree on which that held (every LBVH; a refitted SBVH) keeps it; boxes the SBVH builder clipped
+ * stay as tight as they were where their record is not rewritten. A treelet with fewer than
+ * 3 leaves, an inverted leaf box (lo > hi) or a subset area that is not finite is left bit for
+ * bit, so NaN, infinite and empty boxes never steer a rewrite; so is one whose root would not get
+ * back, bit for bit, the union of its two old boxes (another order of uniting can flip the sign
+ * of a zero plane, and clipped boxes are not the unions of what lies below them): the slot above
+ * the root is never recomputed, and stays what a refit would write. Nodes that are not a tree:
+ * MRTH_ERR_INVALID_ARG, nothing written. info may be NULL. */
+enum { MRTH_OPTIMIZE_MAX_ROUNDS = 8 };
+typedef struct mrth_optimize_info {
+    int32_t rounds;                                /* passes run                                     */
+    int32_t levels;                                /* height levels after the last pass              */
+    int64_t considered[MRTH_OPTIMIZE_MAX_ROUNDS];  /* per pass: records of height >= 1               */
+    int64_t rewritten[MRTH_OPTIMIZE_MAX_ROUNDS];   /* per pass: treelets whose records were rewritten */
+    double  wall_ms;
+} mrth_optimize_info;
+int  mrth_bvh_optimize(mrth_bvh* b, int32_t rounds, mrth_optimize_info* info);
 /* Woop rows (Z,U,V; 12 floats) of one triangle, CudaBVH::woopifyTri. */
 void mrth_woopify(const float v0[3], const float v1[3], const float v2[3], float out[12]);
 
