@@ -242,6 +242,116 @@ def tie_cases():
     return out
 
 
+# ---- the leaf gallery: leaves of 1 to 33 triangles with known answers ---------------------------
+GALLERY_SIZES = (1, 2, 3, 4, 5, 7, 8, 9, 11, 12, 13, 15, 16, 17, 20, 33)
+GALLERY_CELL = 8.0      # cell c lies in y in [8c, 8c + 1]: seven units of nothing between two cells
+GALLERY_LEVELS = 5      # 32 cells under a balanced binary tree: five inner nodes above every leaf
+
+
+def gallery_cells():
+    """(kind, L) per cell, in y order and in the order of the Woop array: a row leaf and a stack
+    leaf per size, the 16-triangle row first (a leaf too long for a count opens the array) and
+    the 33-triangle stack last (nothing follows its terminator)."""
+    rows = [("row", n) for n in GALLERY_SIZES]
+    rows.insert(0, rows.pop(GALLERY_SIZES.index(16)))
+    return rows + [("stack", n) for n in GALLERY_SIZES]
+
+
+def leaf_gallery():
+    """One Compact2 tree whose 32 leaves hold 1 to 33 triangles, every coordinate a multiple of
+    1/8, and rays that put the deciding triangle at every list position of every leaf.
+
+    Each leaf has a cell of its own in y, so a ray down -z aimed at one leaf enters no other
+    leaf's box, and at each of the five levels above it exactly one child box (the boxes are the
+    exact unions of their cells, disjoint in y between siblings).
+
+    Row leaf of L: list position p is the unit right triangle at x in [2p, 2p + 1] in the plane
+    z = -1. Ray p comes down on it from z = 1: the only hit, t = 2, whatever the mode or the order.
+    One more ray comes down between two triangles (beside the hypotenuse of the only one, L = 1),
+    inside the leaf's box: L rejects, a miss that keeps tmax.
+
+    Stack leaf of L: one footprint, list position k in the plane z = -1 - (L - 1 - k) / 4: the
+    farthest first. From z = 1 position k is hit at t = 2 + (L - 1 - k) / 4. The full ray's
+    closest hit is the last position at t = 2; an any-hit ray takes the first accepted in the
+    order tested: position 0 in list order. The short ray j (tmax = 2 + j / 4 + 1 / 8) can
+    accept only the j + 1 nearest, positions L - 1 - j and later: the closest is the last still,
+    the first accepted in list order position L - 1 - j, after L - 1 - j tested rejects. A
+    closest-hit ray cannot leave a leaf it entered (at t = 2 < tmax) before its end: L triangles
+    tested, one leaf finished, five binary nodes fetched; at least two 4-wide nodes, each of which
+    takes in at most three of the five binary ones.
+
+    Returns a dict: bufs; rays float32 [384, 8]; hand [(ray, any_hit, exact (id, t), allowed set
+    or None)] and bounds [(ray, any_hit, binary nodes, wide nodes, triangles, leaves)] as
+    test_gpu_variants.Batch takes them; leaves [(kind, L, leaf ref, ray indices)]."""
+    b = Compact2Builder()
+    cells = gallery_cells()
+    assert len(cells) == 1 << GALLERY_LEVELS
+    next_id = [100]
+    ids, refs = {}, {}
+
+    def cell_box(c):
+        kind, n = cells[c]
+        y = GALLERY_CELL * c
+        if kind == "row":
+            return ((0, y, -1), (2 * n - 1, y + 1, -1))
+        return ((0, y, -1 - (n - 1) / 4), (1, y + 1, -1))
+
+    def make_leaf(c):
+        kind, n = cells[c]
+        y = GALLERY_CELL * c
+        tris = []
+        for k in range(n):
+            x, z = (2.0 * k, -1.0) if kind == "row" else (0.0, -1.0 - (n - 1 - k) / 4)
+            tris.append((next_id[0], (x, y, z), (x + 1, y, z), (x, y + 1, z)))
+            next_id[0] += 7   # distinct, and no id its own list position
+        ids[c] = [t[0] for t in tris]
+        refs[c] = b.leaf(tris)
+        return refs[c]
+
+    def union(lo, hi):
+        boxes = [cell_box(c) for c in range(lo, hi)]
+        return (tuple(min(bx[0][a] for bx in boxes) for a in range(3)),
+                tuple(max(bx[1][a] for bx in boxes) for a in range(3)))
+
+    def build(lo, hi):
+        if hi - lo == 1:
+            return make_leaf(lo)
+        idx = b.reserve_inner()
+        mid = (lo + hi) // 2
+        c0, c1 = build(lo, mid), build(mid, hi)
+        return b.set_inner(idx, union(lo, mid), union(mid, hi), c0, c1)
+
+    build(0, len(cells))
+    bufs = b.buffers()
+    assert ~refs[0] == 0 and len(ids[0]) == 16                           # a long leaf opens the Woop array
+    assert ~refs[len(cells) - 1] + 3 * 33 + 1 == len(bufs[1]) // 4       # and the longest one ends it
+
+    down = (0, 0, -1)
+    rays, hand, bounds, leaves = [], [], [], []
+    for c, (kind, n) in enumerate(cells):
+        y = GALLERY_CELL * c + 0.25
+        first = len(rays)
+        if kind == "row":
+            for p in range(n):
+                for any_hit in (False, True):
+                    hand.append((len(rays), any_hit, (ids[c][p], 2.0), None))
+                rays.append(ray((2 * p + 0.25, y, 1), down))
+            xy = (2 * ((n - 2) // 2) + 1.5, y) if n > 1 else (0.75, y + 0.5)
+            for any_hit in (False, True):
+                hand.append((len(rays), any_hit, (-1, 100.0), None))
+            rays.append(ray((*xy, 1), down))
+        else:
+            at = [(ids[c][k], 2.0 + (n - 1 - k) / 4) for k in range(n)]   # (id, t) per list position
+            for tmax, eligible in [(100.0, 0)] + [(2.0 + j / 4 + 0.125, n - 1 - j) for j in range(n)]:
+                i = len(rays)
+                hand.append((i, False, at[n - 1], None))
+                hand.append((i, True, at[eligible], set(at[eligible:])))
+                bounds.append((i, False, GALLERY_LEVELS, 2, n, 1))
+                rays.append(ray((0.25, y, 1), down, tmax=tmax))
+        leaves.append((kind, n, refs[c], list(range(first, len(rays)))))
+    return dict(bufs=bufs, rays=np.stack(rays), hand=hand, bounds=bounds, leaves=leaves)
+
+
 def scene_comb(depth):
     """A comb of `depth` inner nodes for a stack-depth test (reference STACK_SIZE 64,
     kepler_dynamic_fetch.cu:47). Inner node k (k < depth-1) has child 0 = inner

@@ -6,6 +6,7 @@ import functools
 import numpy as np
 
 import lbvh_util as L
+import leaf_util as LU
 import mrt
 import refit_util as R
 
@@ -26,6 +27,10 @@ for _kind in L.EDGE_GEOMETRY:
     TREES[f"edge-{_kind}"] = (lambda k=_kind: L.host_edge(k, 4))
 for _name, _param in R.SCENES:
     TREES[f"sbvh-{_name}{_param}"] = (lambda n=_name, p=_param: R.built(n, p, ALPHA)[:3])
+# SBVHs whose leaves hold up to 17 and up to 33 triangles (leaf_util.NATURAL)
+BIG_LEAVES = [f"sbvh-{_name}" for _name in LU.NATURAL]
+for _name in LU.NATURAL:
+    TREES[f"sbvh-{_name}"] = (lambda n=_name: LU.built(n))
 
 
 def is_lbvh(name):

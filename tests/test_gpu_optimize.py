@@ -12,7 +12,9 @@ csrc/treelet_kernel.hip) against its CPU statement (Bvh.optimize, tests/test_opt
 "random" 9000 at max_leaf_size 4 (3242 records) has height levels 1-6 (755 .. 68 records) above
 the 64-record threshold between a launch per level and the one-workgroup tail, which takes the
 other eight; at max_leaf_size 1 level 1 has 1988 records, more than the refit's 1024. In "copies"
-every Morton code is equal; "one" and "n_eq_l_plus_1" are a single record.
+every Morton code is equal; "one" and "n_eq_l_plus_1" are a single record. The four trees of
+leaf_util.NATURAL (optimize_util.BIG_LEAVES) have leaves of up to 17 and up to 33 triangles: the
+derived leaf counts of the new tree include 9 to 15 and the 0 of a longer leaf.
 """
 import ctypes as C
 
@@ -127,7 +129,7 @@ def check_closest(rays, got, want, woop, tri):
 
 
 TRACED = ["hairball3-L4", "random1500-L1", "random9000-L4", "copies-L1", "flat-L4", "sbvh-hairball3", "edge-signed_zero",
-          "edge-nonfinite", "one-L4"]
+          "edge-nonfinite", "one-L4"] + U.BIG_LEAVES
 
 
 @pytest.mark.parametrize("name", TRACED)

@@ -215,7 +215,12 @@ def test_the_oracle_on_reference_trees_equals_brute_force(name):
 @pytest.mark.parametrize("name", TREES)
 def test_traces_on_reference_trees_equal_the_oracle(tracer, restore, name, kernel):
     rays, closest, anyhit, _, _ = rays_and_answers(name)
-    bufs = tree(name)[0]
+    check_kernel(tracer, kernel, tree(name)[0], rays, closest, anyhit)
+
+
+def check_kernel(tracer, kernel, bufs, rays, closest, anyhit):
+    """One of KERNELS on a tree, against the oracle's closest and any-hit answers (shared with
+    tests/test_gpu_leaf_sizes.py)."""
     reps = 1
     if kernel == "oneshot":     # that kernel runs only grids larger than the resident lanes
         resident = torch.cuda.get_device_properties(0).multi_processor_count * RESIDENT_LANES_PER_CU

@@ -1,6 +1,7 @@
 """Every instantiated traversal kernel (mrt_trace_kernel_keys: 136) on the hand-derived answers of
-tests/kat.py, on stacks that spill, on a tree every node of which must be visited, and on the
-special-value, on-surface and incoherent rays of test_gpu_parity.py; and the edge rays across the
+tests/kat.py, on stacks that spill, on a tree every node of which must be visited, on the
+special-value, on-surface and incoherent rays of test_gpu_parity.py, and on leaves of up to 33
+triangles (kat.leaf_gallery and an SBVH built with min_leaf 17); and the edge rays across the
 launch schedules on the four production kernels.
 
 Each case sets the configuration that selects one kernel, checks after every launch that this
@@ -34,6 +35,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import kat  # noqa: E402
+import leaf_util  # noqa: E402
 import oracle_lib as O  # noqa: E402
 from test_abi import expected_kernel_keys  # noqa: E402
 from test_gpu_backfill import SENTINEL, assert_matches_oracle, cus, restore, tracer  # noqa: E402,F401
@@ -138,6 +140,17 @@ def batches():
         b.capped[:lo] = True
         b.capped[len(b.rays) - 2000:] = True
         _BATCHES.append(b)
+    # leaves of 1 to 33 triangles (every other batch: 8 at the most), the deciding triangle at every
+    # list position: the counted leaf loop's two exits, counts 9 to 15 and the 0 of a longer leaf,
+    # the tail's chunks of four, the uncounted loops' prefetch past the end of the Woop array
+    g = leaf_util.gallery()
+    b = Batch("leaf-gallery", tuple(np.array(a) for a in g["bufs"]), g["rays"])
+    b.hand, b.bounds = list(g["hand"]), list(g["bounds"])
+    _BATCHES.append(b)
+    # an SBVH with leaves of 5 to 17 triangles, a 64 x 48 frame and 1000 incoherent rays; no count
+    # cap: every differing quantized result must be a valid closer hit
+    name = "random1500-min17"
+    _BATCHES.append(Batch(name, tuple(np.array(a) for a in leaf_util.buffers(name)), leaf_util.rays_for(name)))
     return _BATCHES
 
 
