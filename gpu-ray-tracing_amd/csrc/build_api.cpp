@@ -140,38 +140,25 @@ int build_impl(mrt_tracer* t, const float* vertices, int64_t numVertices, const 
     const int64_t slots = 3 * (int64_t)n + leaves;
 
     // The level plan of the emitted topology: on the device, kept as the tracer's refit plan, or
-    // on the host (the call is synchronous for it).
+    // on the host (the call is synchronous for it; so above MRT_DERIVE_MAX_LEVELS depth levels).
+    static const char* const kPrefix = "build: the emitted nodes are not a tree: ";
     const auto tPlan = std::chrono::steady_clock::now();
-    mrt::DeriveRun run;
-    mrt::RefitPlan plan;
-    mrt::RefitLevels lv;
+    mrt::Derivation d;
+    mrt::RefitPlan& plan = d.plan;
     bool derived = false;
     if (onDevice) {
-        int status = mrt::kDeriveOk;
-        const char* why = nullptr;
-        if (int rc = mrt::derive_begin(run, nodes, records, s)) return rc;
-        if (int rc = mrt::derive_plan(run, &plan, s, &status, &why)) return rc;
-        if (status == mrt::kDeriveMalformed)
-            return fail(MRT_ERR_HIP, std::string("build: the emitted nodes are not a tree: ") + why);
-        derived = status == mrt::kDeriveOk;   // else above MRT_DERIVE_MAX_LEVELS depth levels: the host path
-        if (derived) {
-            lv.offsets = plan.levels;
-            orderDev = plan.order.get();
-            offsetsDev = plan.offsets.get();
-            skippedDev = plan.skipped.get();
-        }
+        if (int rc = mrt::derive(d, nodes, records, s, MRT_ERR_HIP, kPrefix)) return rc;
+        derived = !d.tooDeep;
     }
-    if (!derived) {
-        std::vector<int32_t> host((size_t)records * 16);
-        MRT_HIP(hipMemcpyAsync(host.data(), nodes, host.size() * 4, hipMemcpyDeviceToHost, s));
-        MRT_HIP(hipStreamSynchronize(s));
-        if (const char* why = mrt::refit_levels(host.data(), records, &lv))
-            return fail(MRT_ERR_HIP, std::string("build: the emitted nodes are not a tree: ") + why);
-        const std::vector<int32_t> offsets(lv.offsets.begin(), lv.offsets.end());
-        MRT_HIP(hipMemcpyAsync(orderDev, lv.order.data(), lv.order.size() * 4, hipMemcpyHostToDevice, s));
-        MRT_HIP(hipMemcpyAsync(offsetsDev, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice, s));
-        MRT_HIP(hipMemsetAsync(skippedDev, 0, sizeof(unsigned long long), s));
-        MRT_HIP(hipStreamSynchronize(s));   // the uploads read lv and offsets
+    if (derived) {
+        orderDev = plan.order.get();
+        offsetsDev = plan.offsets.get();
+        skippedDev = plan.skipped.get();
+    } else {
+        mrt::RefitLevels lv;
+        if (int rc = mrt::host_levels(nodes, records, s, MRT_ERR_HIP, kPrefix, &lv)) return rc;
+        if (int rc = mrt::upload_levels(lv, orderDev, offsetsDev, skippedDev, s)) return rc;
+        plan.levels = lv.offsets;
     }
     const double planMs = mrt::ms_since(tPlan);
 
@@ -190,7 +177,7 @@ int build_impl(mrt_tracer* t, const float* vertices, int64_t numVertices, const 
     a.skipped = skippedDev;
     int launches = 0;
     MRT_HIP(hipEventRecord(tmp.ev[3], s));
-    if (int rc = mrt::enqueue_refit(a, lv.offsets, orderDev, offsetsDev, s, &launches)) return rc;
+    if (int rc = mrt::enqueue_refit(a, plan.levels, orderDev, offsetsDev, s, &launches)) return rc;
     if (single) MRT_HIP(mrt::launch_lbvh_empty_leaf_box(b.nodes, s));
     MRT_HIP(hipEventRecord(tmp.ev[4], s));
     unsigned long long skipped = 0;
@@ -203,30 +190,24 @@ int build_impl(mrt_tracer* t, const float* vertices, int64_t numVertices, const 
     MRT_HIP(hipEventElapsedTime(&info.emit_ms, tmp.ev[1], tmp.ev[2]));
     MRT_HIP(hipEventElapsedTime(&info.fit_ms, tmp.ev[3], tmp.ev[4]));
 
-    if (derived) {
-        if (int rc = mrt::bind_derived(t, run, std::move(plan), nodes, (int64_t)records * 64, woop, slots * 16, triIndex,
-                                       slots * 4, s)) {
-            mrt::unbind_locked(t);
-            return rc;
-        }
-    } else {
-        if (int rc = mrt::bind_locked(t, nodes, (int64_t)records * 64, woop, slots * 16, triIndex, slots * 4)) return rc;
-        if (onDevice) (void)mrt::derive_report(t, run, false, false, 0.0);
-    }
+    // The buffers are written: a bind that fails leaves the tracer unbound.
+    const mrt::BvhBuffers built{nodes, (int64_t)records * 64, woop, slots * 16, triIndex, slots * 4};
+    const int32_t levels = (int32_t)plan.levels.size() - 1;   // the install takes the plan
+    if (int rc = mrt::install(t, built, onDevice ? &d : nullptr, s, mrt::kUnbindOnError)) return rc;
     info.plan_ms = planMs;
     info.bind_ms = t->bindMs;
-    info.levels = lv.levels();
+    info.levels = levels;
     info.records = records;
     info.leaves = leaves;
     info.slots = slots;
-    info.scratch_bytes = (int64_t)(total + run.scratchBytes);
+    info.scratch_bytes = (int64_t)(total + d.run.scratchBytes);
     info.skipped_refs = (int64_t)skipped;
     info.max_leaf_size = maxLeaf;
     info.wall_ms = mrt::ms_since(t0);
     t->lastBuild = info;
-    *nodeBytes = (int64_t)records * 64;
-    *woopBytes = slots * 16;
-    *triIndexBytes = slots * 4;
+    *nodeBytes = built.nodeBytes;
+    *woopBytes = built.woopBytes;
+    *triIndexBytes = built.triIndexBytes;
     return MRT_OK;
 }
 

@@ -1,6 +1,6 @@
 // derive_api.cpp — the refit plan and the exact 4-wide array of a Compact2 tree derived on the
-// device: the sequence of wide_kernel.hip's launches (derive_begin / derive_plan / bind_derived,
-// which build_api.cpp and refit_api.cpp call too) behind mrt_tracer_bind_device / _derive_info /
+// device: the sequence of wide_kernel.hip's launches (derive / derive_wide, which bind_api.cpp's
+// install, build_api.cpp, refit_api.cpp and optimize_api.cpp call too) behind mrt_tracer_bind_device / _derive_info /
 // _copy_refit_plan. Host work per call is O(depth levels): one launch per level or per run of
 // small levels and pass, one fixed-size summary read back per topology launch, then a few
 // summaries and four bytes per level. No node array crosses to the host.
@@ -45,8 +45,6 @@ int run_pass(DeriveRun& r, DeriveStep step, int dir, hipStream_t s) {
     return MRT_OK;
 }
 
-}  // namespace
-
 int derive_begin(DeriveRun& r, const void* nodes, int64_t numNodes, hipStream_t s) {
     if (!nodes || numNodes < 1 || numNodes > ((int64_t)1 << 26)) return fail(MRT_ERR_INVALID_ARG, "derive: no nodes, or more than 2^26");
     size_t bytes = 0, primBytes = 0;
@@ -60,8 +58,9 @@ int derive_begin(DeriveRun& r, const void* nodes, int64_t numNodes, hipStream_t 
     return MRT_OK;
 }
 
-int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, int* status, const char** why) {
-    *status = kDeriveOk;
+// Fills p (not built) or sets *tooDeep; *why = refit_levels' reason where the nodes are no tree.
+int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, bool* tooDeep, const char** why) {
+    *tooDeep = false;
     *why = nullptr;
     const int n = r.d.numNodes;
     int32_t sum[wide::kSummaryWords] = {};
@@ -77,7 +76,7 @@ int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, int* status, const ch
             return fail(MRT_ERR_HIP, "derive: the topology pass did not end");
         const bool chain = end - begin <= kDeriveChainNodes;
         if (!chain && level >= MRT_DERIVE_MAX_LEVELS) {
-            *status = kDeriveTooDeep;
+            *tooDeep = true;
             return MRT_OK;
         }
         if (chain) MRT_HIP(launch_derive_expand_chain(r.d, r.x.depthOffsets, level, begin, end, MRT_DERIVE_MAX_LEVELS, s));
@@ -95,7 +94,7 @@ int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, int* status, const ch
             end = e;
             if (begin == end) break;   // the last level's end is written: done
             if (level >= MRT_DERIVE_MAX_LEVELS) {
-                *status = kDeriveTooDeep;
+                *tooDeep = true;
                 return MRT_OK;
             }
         } else {
@@ -104,10 +103,7 @@ int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, int* status, const ch
             level++;
         }
     }
-    if ((*why = wide::error_text(sum[wide::kError], sum[wide::kReached], n))) {
-        *status = kDeriveMalformed;
-        return MRT_OK;
-    }
+    if ((*why = wide::error_text(sum[wide::kError], sum[wide::kReached], n))) return MRT_OK;
     r.depthLevels = level;
     r.depth.assign((size_t)level + 1, 0);
     MRT_HIP(hipMemcpyAsync(r.depth.data(), r.x.depthOffsets, r.depth.size() * 4, hipMemcpyDeviceToHost, s));
@@ -144,11 +140,19 @@ int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, int* status, const ch
     return MRT_OK;
 }
 
-namespace {
+}  // namespace
 
-// The exact 4-wide array of r's tree (its plan derived, its boxes final) into w. *kept = false
-// where the stack bound is above the limit: no array, the binary traversal stays.
-int derive_wide(DeriveRun& r, const void* woop, int64_t woopBytes, WideArray* w, bool* kept, hipStream_t s) {
+int derive(Derivation& d, const void* nodes, int64_t numNodes, hipStream_t s, int code, const char* prefix) {
+    const char* why = nullptr;
+    if (int rc = derive_begin(d.run, nodes, numNodes, s)) return rc;
+    if (int rc = derive_plan(d.run, &d.plan, s, &d.tooDeep, &why)) return rc;
+    return why ? fail(code, std::string(prefix) + why) : MRT_OK;
+}
+
+// The exact 4-wide array of r's tree (its plan derived, its boxes final) into w; no array where
+// the stack bound is above the limit: the binary traversal stays.
+int derive_wide(DeriveRun& r, const BvhBuffers& b, WideArray* w, hipStream_t s) {
+    *w = WideArray{};
     const int n = r.d.numNodes;
     int32_t sum[wide::kSummaryWords] = {};
     int32_t numWide = 0;
@@ -162,14 +166,14 @@ int derive_wide(DeriveRun& r, const void* woop, int64_t woopBytes, WideArray* w,
     if (w->bytes > kMaxBufferBytes) return fail(MRT_ERR_TOO_LARGE, "4-wide node array above the 32-bit range");
     if (int rc = run_pass(r, kStepIndex, +1, s)) return rc;
     MRT_HIP(w->nodes.alloc((size_t)w->bytes));
-    MRT_HIP(w->srcDev.alloc((size_t)numWide * 16));
-    const int64_t slots = woopBytes / 16;
+    MRT_HIP(w->src.alloc((size_t)numWide * 16));
+    const int64_t slots = b.woopBytes / 16;
     w->leafCounts = leaf_counts_fit(slots);
-    r.d.woopX = w->leafCounts ? static_cast<const int32_t*>(woop) : nullptr;
+    r.d.woopX = w->leafCounts ? static_cast<const int32_t*>(b.woop) : nullptr;
     r.d.woopStride = 4;
     r.d.woopSlots = slots;
     r.d.wideOut = w->nodes.get();
-    r.d.srcOut = w->srcDev.get();
+    r.d.srcOut = w->src.get();
     r.d.numWide = numWide;
     MRT_HIP(hipEventRecord(r.ev[3], s));
     MRT_HIP(launch_derive_emit(r.d, s));
@@ -177,16 +181,17 @@ int derive_wide(DeriveRun& r, const void* woop, int64_t woopBytes, WideArray* w,
     MRT_HIP(hipEventRecord(r.ev[4], s));
     if (int rc = read_summary(r, sum, s)) return rc;
     const int64_t need = sum[wide::kStackBound];
-    *kept = need >= 0 && need + 1 <= kMaxWideStack;
-    w->format = kNodeWide4;
-    w->stackCap = std::max<int>(kStackCapacity, (int)need + 1);
-    w->stackBound = (int)need;
+    if (need < 0 || need + 1 > kMaxWideStack) *w = WideArray{};
+    else {
+        w->format = kNodeWide4;
+        w->stackCap = std::max<int>(kStackCapacity, (int)need + 1);
+        w->stackBound = (int)need;
+    }
+    w->builtFor = 1;
     return MRT_OK;
 }
 
-}  // namespace
-
-int derive_report(mrt_tracer* t, const DeriveRun& r, bool plan, bool wide, double wallMs) {
+int derive_report(const DeriveRun& r, bool plan, bool wide, mrt_derive_info* out) {
     mrt_derive_info info{};
     info.on_device_plan = plan;
     info.on_device_wide = wide;
@@ -200,60 +205,9 @@ int derive_report(mrt_tracer* t, const DeriveRun& r, bool plan, bool wide, doubl
         MRT_HIP(hipEventElapsedTime(&info.collapse_ms, r.ev[2], r.ev[3]));
         MRT_HIP(hipEventElapsedTime(&info.emit_ms, r.ev[3], r.ev[4]));
     }
-    info.wall_ms = wallMs;
     info.scratch_bytes = (int64_t)r.scratchBytes;
-    t->lastDerive = info;
+    *out = info;
     return MRT_OK;
-}
-
-int bind_derived(mrt_tracer* t, DeriveRun& r, RefitPlan&& p, const void* nodes, int64_t nodeBytes, const void* woop,
-                 int64_t woopBytes, const int32_t* triIndex, int64_t triIndexBytes, hipStream_t s, bool keepTunes) {
-    const auto t0 = std::chrono::steady_clock::now();
-    t->nodes = nodes;
-    t->nodeBytes = nodeBytes;
-    t->woop = woop;
-    t->woopBytes = woopBytes;
-    t->triIndex = triIndex;
-    t->triIndexBytes = triIndexBytes;
-    t->bound = true;
-    if (!keepTunes) tune_reset(t);
-    drop_plan(t);
-    // launches in flight may still read the old wide array: wait for this handle's own
-    if (int rc = wait_all_workspaces(t)) return rc;
-    MRT_HIP(t->wide.nodes.free());
-    t->wide = WideArray{};
-    const int want = t->cfg.wide;
-    bool wideOnDevice = false;
-    if (want == 1) {
-        WideArray w;
-        bool kept = false;
-        if (int rc = derive_wide(r, woop, woopBytes, &w, &kept, s)) return rc;
-        wideOnDevice = kept;
-        if (kept) {
-            p.bytes += (int64_t)r.d.numWide * 16;
-            t->wide = std::move(w);   // complete, or not held at all
-        }
-        t->wide.builtFor = want;
-    } else {
-        t->wide.builtFor = -1;
-        if (int rc = refresh_wide(t)) return rc;   // cfg.wide 2: the quantized form through the host path
-        const WideArray& w = t->wide;
-        if (w.nodes && w.format == kNodeWide4 && !w.src.empty()) {   // no finite quantization: the exact form
-            MRT_HIP(p.wideSrc.alloc(w.src.size() * 4));
-            MRT_HIP(hipMemcpy(p.wideSrc.get(), w.src.data(), w.src.size() * 4, hipMemcpyHostToDevice));
-            p.bytes += (int64_t)w.src.size() * 4;
-        }
-    }
-    MRT_HIP(hipStreamSynchronize(s));   // the plan's uploads read r; the events are complete
-    p.built = true;
-    t->plan = std::move(p);
-    t->bindMs = ms_since(t0);
-    return derive_report(t, r, true, wideOnDevice, t->bindMs);
-}
-
-const int32_t* refit_wide_src(const mrt_tracer* t) {
-    if (!t->wide.nodes || t->wide.format != kNodeWide4) return nullptr;
-    return t->plan.wideSrc ? t->plan.wideSrc.get() : t->wide.srcDev.get();
 }
 
 }  // namespace mrt
@@ -262,35 +216,19 @@ extern "C" {
 
 int mrt_tracer_bind_device(mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
                            const int32_t* triIndex, int64_t triIndexBytes, void* stream) {
-    if (int rc = mrt::check_bind_args(t, nodes, nodeBytes, woop, woopBytes, triIndex, triIndexBytes)) return rc;
+    const mrt::BvhBuffers b{nodes, nodeBytes, woop, woopBytes, triIndex, triIndexBytes};
+    if (int rc = mrt::check_bind_args(t, b)) return rc;
     std::lock_guard<std::mutex> lock(t->mu);
     DeviceGuard guard(t->device);
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = static_cast<hipStream_t>(stream);
-    mrt::DeriveRun r;
-    mrt::RefitPlan p;
-    int status = mrt::kDeriveOk;
-    const char* why = nullptr;
-    if (int rc = mrt::derive_begin(r, nodes, nodeBytes / 64, s)) return rc;
-    if (int rc = mrt::derive_plan(r, &p, s, &status, &why)) {
-        mrt::unbind_locked(t);
+    mrt::Derivation d;
+    if (int rc = mrt::derive(d, b.nodes, b.numNodes(), s, MRT_ERR_INVALID_ARG, "bind_device: the nodes are not a tree: ")) {
+        (void)mrt::unbind_locked(t);   // mrt.h: a refused tree leaves the tracer unbound
         return rc;
     }
-    if (status == mrt::kDeriveMalformed) {
-        mrt::unbind_locked(t);
-        return fail(MRT_ERR_INVALID_ARG, std::string("bind_device: the nodes are not a tree: ") + why);
-    }
-    if (status == mrt::kDeriveTooDeep) {   // the host path, and the info says so
-        if (int rc = mrt::bind_locked(t, nodes, nodeBytes, woop, woopBytes, triIndex, triIndexBytes)) return rc;
-        return mrt::derive_report(t, r, false, false, mrt::ms_since(t0));
-    }
-    if (int rc = mrt::bind_derived(t, r, std::move(p), nodes, nodeBytes, woop, woopBytes, triIndex, triIndexBytes, s)) {
-        mrt::unbind_locked(t);
-        return rc;
-    }
-    t->bindMs = mrt::ms_since(t0);
-    t->lastDerive.wall_ms = t->bindMs;
-    return MRT_OK;
+    // too deep: the host path, and the info says so
+    return mrt::install(t, b, &d, s, mrt::kUnbindOnError, &t0);
 }
 
 int mrt_tracer_derive_info(mrt_tracer* t, mrt_derive_info* info) {
@@ -319,7 +257,7 @@ int mrt_tracer_copy_refit_plan(mrt_tracer* t, int32_t* order, int64_t* levelOffs
         MRT_HIP(hipMemcpy(dev.data(), p.offsets.get(), dev.size() * 4, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < dev.size(); i++) levelOffsets[i] = dev[i];
     }
-    const int32_t* src = mrt::refit_wide_src(t);
+    const int32_t* src = t->wide.src.get();
     if (numWideSrc && src) {
         *numWideSrc = t->wide.bytes / 128 * 4;
         if (wideSrc) {

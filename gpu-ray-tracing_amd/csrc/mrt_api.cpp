@@ -311,7 +311,7 @@ int check_call(const mrt_tracer* t, int32_t numRays, uint32_t flags) {
 
 int check_batch(const mrt_tracer* t, const void* rays, const void* results, int32_t numRays, uint32_t flags,
                 const int32_t* stats) {
-    if (!t->bound) return fail(MRT_ERR_NOT_BOUND, "trace before bind (no BVH)");
+    if (!t->bvh) return fail(MRT_ERR_NOT_BOUND, "trace before bind (no BVH)");
     if (!rays || !results) return fail(MRT_ERR_INVALID_ARG, "null ray/result buffer");
     if ((flags & MRT_TRACE_STATS) && !stats) return fail(MRT_ERR_INVALID_ARG, "MRT_TRACE_STATS without stats buffer");
     if (numRays > kMaxRaysPerLaunch) return fail(MRT_ERR_TOO_LARGE, "more than 2^30 rays in one launch: split the batch");
@@ -324,11 +324,11 @@ mrt::TraceArgs trace_args(const mrt_tracer* t, const mrt_launch_cfg& cfg, const 
                           const mrt::Workspace* ws, int numRays, int totalLanes, int stackCap, bool blocking) {
     const bool wide = v.nodes != mrt::kNodeCompact2;
     mrt::TraceArgs a{};
-    a.nodes = static_cast<const float4*>(wide ? t->wide.nodes.get() : t->nodes);
-    a.woop = static_cast<const float4*>(t->woop);
-    a.triIndex = t->triIndex;
-    a.nodeBytes = (uint32_t)(wide ? t->wide.bytes : t->nodeBytes);
-    a.woopBytes = (uint32_t)t->woopBytes;
+    a.nodes = static_cast<const float4*>(wide ? t->wide.nodes.get() : t->bvh.nodes);
+    a.woop = static_cast<const float4*>(t->bvh.woop);
+    a.triIndex = t->bvh.triIndex;
+    a.nodeBytes = (uint32_t)(wide ? t->wide.bytes : t->bvh.nodeBytes);
+    a.woopBytes = (uint32_t)t->bvh.woopBytes;
     a.numRays = numRays;
     a.numQueues = cfg.num_queues < 0 ? 0 : std::min(cfg.num_queues, std::max(1, numRays));
     // queue_shared percent of the rays past the first round go to the shared queue
@@ -411,7 +411,7 @@ int trace_impl(mrt_tracer* t, const void* rays, void* results, int32_t numRays, 
 
     DeviceGuard guard(t->device);
     mrt::TraceVariant v = variant_for(t, flags);   // its key (the tracer's tail setting) keys the tuning
-    mrt_launch_cfg cfg = mrt::effective_cfg(t->cfg, t->numCUs, t->nodeBytes + t->woopBytes, numRays);
+    mrt_launch_cfg cfg = mrt::effective_cfg(t->cfg, t->numCUs, t->bvh.nodeBytes + t->bvh.woopBytes, numRays);
     // autotuning: the schedule candidate this launch uses, and the slot and events of its timing
     mrt::TuneState* tune = t->tunes.lookup(t->cfg, cfg, flags, numRays, variant_key(v), stream);
     int cand = -1, slot = -1;
@@ -539,14 +539,12 @@ int mrt_tracer_create(int device, mrt_tracer** out) {
 int mrt_tracer_destroy(mrt_tracer* t) {
     if (!t) return MRT_OK;
     {
-        // each owner lets go after the wait that makes it safe, in this order
+        // each owner lets go after the wait that makes it safe (unbind: event waits, the streams
+        // may already be destroyed; the plan, the wide array, the tuned schedules)
         DeviceGuard guard(t->device);
-        mrt::drop_plan(t);
-        t->wide = mrt::WideArray{};
-        (void)mrt::wait_all_workspaces(t);   // event waits: the streams may already be destroyed
+        (void)mrt::unbind_locked(t);
         t->workspaces.clear();
         t->blocking = mrt::EventPair{};
-        mrt::tune_reset(t);
     }
     delete t;
     return MRT_OK;
@@ -558,14 +556,7 @@ int mrt_tracer_set_config(mrt_tracer* t, const mrt_launch_cfg* cfg) {
     if (!mrt::valid_cfg(c)) return fail(MRT_ERR_INVALID_ARG, "launch config out of range");
     std::lock_guard<std::mutex> lock(t->mu);
     t->cfg = c;
-    DeviceGuard guard(t->device);
-    mrt::tune_reset(t);
-    mrt::drop_plan(t);
-    const auto t0 = std::chrono::steady_clock::now();
-    const int built = t->wide.builtFor;
-    const int rc = mrt::refresh_wide(t);
-    if (t->wide.builtFor != built) t->bindMs = mrt::ms_since(t0);
-    return rc;
+    return mrt::refresh_wide(t, false);   // the plan and the schedules go; the wide array if cfg.wide changed
 }
 
 int mrt_tracer_get_config(const mrt_tracer* t, mrt_launch_cfg* cfg) {

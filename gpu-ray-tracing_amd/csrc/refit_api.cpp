@@ -19,33 +19,24 @@ int wait_refit(mrt_tracer* t) {
     return MRT_OK;
 }
 
-// bind, unbind, set_config, destroy and build_plan.
-void drop_plan(mrt_tracer* t) {
-    (void)wait_refit(t);   // a refit may still read the plan
-    t->plan = RefitPlan{};
+int host_levels(const void* nodes, int64_t numNodes, hipStream_t s, int code, const char* prefix, RefitLevels* lv) {
+    std::vector<int32_t> host((size_t)numNodes * 16);
+    MRT_HIP(hipMemcpyAsync(host.data(), nodes, host.size() * 4, hipMemcpyDeviceToHost, s));
+    MRT_HIP(hipStreamSynchronize(s));
+    if (const char* why = refit_levels(host.data(), numNodes, lv)) return fail(code, std::string(prefix) + why);
+    return MRT_OK;
+}
+
+int upload_levels(const RefitLevels& lv, int32_t* order, int32_t* offsets, unsigned long long* skipped, hipStream_t s) {
+    const std::vector<int32_t> offsets32(lv.offsets.begin(), lv.offsets.end());   // < 2^26 nodes
+    MRT_HIP(hipMemcpyAsync(order, lv.order.data(), lv.order.size() * 4, hipMemcpyHostToDevice, s));
+    MRT_HIP(hipMemcpyAsync(offsets, offsets32.data(), offsets32.size() * 4, hipMemcpyHostToDevice, s));
+    MRT_HIP(hipMemsetAsync(skipped, 0, sizeof(unsigned long long), s));
+    MRT_HIP(hipStreamSynchronize(s));   // the uploads read lv and offsets32
+    return MRT_OK;
 }
 
 namespace {
-
-template <class T>
-int upload(DeviceBuf<T>* dst, const std::vector<T>& src) {
-    MRT_HIP(dst->alloc(src.size() * sizeof(T)));
-    MRT_HIP(hipMemcpy(dst->get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MRT_OK;
-}
-
-// The wide source map of a host-derived exact array goes to the device with the plan; a
-// device-derived one is there already (WideArray::srcDev).
-int attach_wide_src(const mrt_tracer* t, RefitPlan* p) {
-    const WideArray& w = t->wide;
-    if (w.nodes && w.format == kNodeWide4 && (int64_t)w.src.size() == w.bytes / 128 * 4) {
-        if (int rc = upload(&p->wideSrc, w.src)) return rc;
-        p->bytes += (int64_t)w.src.size() * 4;
-    } else if (w.nodes && w.format == kNodeWide4 && w.srcDev) {
-        p->bytes += w.bytes / 128 * 4 * 4;
-    }
-    return MRT_OK;
-}
 
 // Builds the refit plan of the bound tree (the handle's mutex held) on the device
 // (derive_api.cpp: no node array crosses to the host). Synchronous. A tree of more than
@@ -53,70 +44,48 @@ int attach_wide_src(const mrt_tracer* t, RefitPlan* p) {
 // once for their child refs (topology only: a refit in flight changes boxes, never words 12-15).
 int build_plan(mrt_tracer* t) {
     if (t->plan.built) return MRT_OK;
-    const int64_t numNodes = t->nodeBytes / 64;
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        DeriveRun r;
-        RefitPlan p;
-        int status = kDeriveOk;
-        const char* why = nullptr;
-        if (int rc = derive_begin(r, t->nodes, numNodes, nullptr)) return rc;
-        if (int rc = derive_plan(r, &p, nullptr, &status, &why)) return rc;
-        if (status == kDeriveMalformed)
-            return fail(MRT_ERR_INVALID_ARG, std::string("refit: the bound nodes are not a tree: ") + why);
-        if (status == kDeriveOk) {
-            MRT_HIP(hipStreamSynchronize(nullptr));   // the offsets' upload reads r
-            drop_plan(t);
-            if (int rc = attach_wide_src(t, &p)) return rc;
-            p.built = true;
-            t->plan = std::move(p);   // complete, or not held at all
-            return derive_report(t, r, true, false, ms_since(t0));
-        }
+    static const char* const kPrefix = "refit: the bound nodes are not a tree: ";
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t numNodes = t->bvh.numNodes();
+    Derivation d;
+    RefitPlan& p = d.plan;
+    mrt_derive_info info{};
+    if (int rc = derive(d, t->bvh.nodes, numNodes, nullptr, MRT_ERR_INVALID_ARG, kPrefix)) return rc;
+    if (d.tooDeep) {
+        RefitLevels lv;
+        if (int rc = host_levels(t->bvh.nodes, numNodes, nullptr, MRT_ERR_INVALID_ARG, kPrefix, &lv)) return rc;
+        MRT_HIP(p.order.alloc(lv.order.size() * 4));
+        MRT_HIP(p.offsets.alloc(lv.offsets.size() * 4));
+        MRT_HIP(p.valid.alloc((size_t)numNodes * 2));
+        MRT_HIP(p.skipped.alloc(sizeof(unsigned long long)));
+        if (int rc = upload_levels(lv, p.order.get(), p.offsets.get(), p.skipped.get(), nullptr)) return rc;
+        p.bytes = (int64_t)lv.order.size() * 4 + (int64_t)lv.offsets.size() * 4 + numNodes * 2 + 8;
+        p.levels = lv.offsets;
     }
-    std::vector<int32_t> host((size_t)(t->nodeBytes / 4));
-    MRT_HIP(hipMemcpy(host.data(), t->nodes, (size_t)t->nodeBytes, hipMemcpyDeviceToHost));
-    RefitLevels lv;
-    if (const char* why = refit_levels(host.data(), numNodes, &lv))
-        return fail(MRT_ERR_INVALID_ARG, std::string("refit: the bound nodes are not a tree: ") + why);
-    const std::vector<int32_t> offsets(lv.offsets.begin(), lv.offsets.end());   // < 2^26 nodes
-    drop_plan(t);
-    RefitPlan p;
-    if (int rc = upload(&p.order, lv.order)) return rc;
-    if (int rc = upload(&p.offsets, offsets)) return rc;
-    MRT_HIP(p.valid.alloc((size_t)numNodes * 2));
-    MRT_HIP(p.skipped.alloc(sizeof(unsigned long long)));
-    MRT_HIP(hipMemset(p.skipped.get(), 0, sizeof(unsigned long long)));
-    p.bytes = (int64_t)lv.order.size() * 4 + (int64_t)offsets.size() * 4 + numNodes * 2 + 8;
-    if (int rc = attach_wide_src(t, &p)) return rc;
-    p.levels = lv.offsets;
+    MRT_HIP(hipStreamSynchronize(nullptr));   // the offsets' upload reads d.run
+    if (int rc = derive_report(d.run, !d.tooDeep, false, &info)) return rc;   // too deep: the info says so
     p.built = true;
-    t->plan = std::move(p);   // complete, or not held at all
-    return MRT_OK;
+    Install in;
+    in.plan = &p;   // complete, or not held at all
+    in.derive = &info;
+    in.since = &t0;
+    in.keepTunes = true;
+    return commit(t, t->bvh, in);
 }
 
 }  // namespace
 
-// The Woop rows and boxes of the Compact2 buffers in `a`, bound or not: the leaves, one launch
-// per level above kRefitTailNodes nodes, one workgroup for all smaller levels. levels: the
-// plan's offsets on the host; order / offsets: the plan on the device.
+// The Woop rows and boxes of the Compact2 buffers in `a`, bound or not: the leaves, then the
+// inner levels (walk_levels above kRefitTailNodes nodes). levelOffsets: the plan's offsets on
+// the host; order / offsets: the plan on the device.
 int enqueue_refit(const RefitArgs& a, const std::vector<int64_t>& levelOffsets, const int32_t* order,
                   const int32_t* offsets, hipStream_t s, int* launches) {
     MRT_HIP(launch_refit_leaves(a, s));
     ++*launches;
-    const int levels = (int)levelOffsets.size() - 1;
-    for (int l = 1; l < levels; l++) {
-        const int begin = (int)levelOffsets[(size_t)l], count = (int)(levelOffsets[(size_t)l + 1] - begin);
-        if (count > kRefitTailNodes) {
-            MRT_HIP(launch_refit_level(a, order, begin, count, s));
-            ++*launches;
-            continue;
-        }
-        // level sizes never grow with the height: this one and all above it fit one workgroup
-        MRT_HIP(launch_refit_tail(a, order, offsets, l, levels, s));
-        ++*launches;
-        break;
-    }
-    return MRT_OK;
+    return walk_levels(
+        levelOffsets, kRefitTailNodes, launches,
+        [&](int begin, int count) { return launch_refit_level(a, order, begin, count, s); },
+        [&](int first, int levels) { return launch_refit_tail(a, order, offsets, first, levels, s); });
 }
 
 }  // namespace mrt
@@ -129,7 +98,7 @@ int mrt_tracer_refit(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     if (numVertices < 0 || numTriangles < 0 || (numVertices && !vertices) || (numTriangles && !triangles))
         return fail(MRT_ERR_INVALID_ARG, "refit: bad vertex / triangle arrays");
     std::lock_guard<std::mutex> lock(t->mu);
-    if (!t->bound) return fail(MRT_ERR_NOT_BOUND, "refit before bind (no BVH)");
+    if (!t->bvh) return fail(MRT_ERR_NOT_BOUND, "refit before bind (no BVH)");
     DeviceGuard guard(t->device);
     if (int rc = mrt::build_plan(t)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -137,11 +106,11 @@ int mrt_tracer_refit(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     mrt::WideArray& wide = t->wide;
 
     mrt::RefitArgs a{};
-    a.nodes = static_cast<uint32_t*>(const_cast<void*>(t->nodes));   // refit writes the bound buffers (mrt.h)
-    a.numNodes = (int)(t->nodeBytes / 64);
-    a.woop = static_cast<uint32_t*>(const_cast<void*>(t->woop));
-    a.woopSlots = (int)(t->woopBytes / 16);
-    a.triIndex = t->triIndex;
+    a.nodes = static_cast<uint32_t*>(const_cast<void*>(t->bvh.nodes));   // refit writes the bound buffers (mrt.h)
+    a.numNodes = (int)t->bvh.numNodes();
+    a.woop = static_cast<uint32_t*>(const_cast<void*>(t->bvh.woop));
+    a.woopSlots = (int)(t->bvh.woopBytes / 16);
+    a.triIndex = t->bvh.triIndex;
     a.vertices = vertices;
     a.numVertices = numVertices;
     a.triangles = triangles;
@@ -152,22 +121,18 @@ int mrt_tracer_refit(mrt_tracer* t, const float* vertices, int64_t numVertices, 
     int launches = 0;
     plan.launched = true;
     if (int rc = mrt::enqueue_refit(a, plan.levels, plan.order.get(), plan.offsets.get(), s, &launches)) return rc;
-    if (const int32_t* wideSrc = mrt::refit_wide_src(t)) {
-        MRT_HIP(mrt::launch_refit_wide(a, wideSrc, wide.nodes.get(), (int)(wide.bytes / 128), s));
+    if (wide.src) {
+        MRT_HIP(mrt::launch_refit_wide(a, wide.src.get(), wide.nodes.get(), (int)(wide.bytes / 128), s));
         launches++;
     }
     plan.launches = launches;
     if (wide.nodes && wide.format == mrt::kNodeWide4Q) {
         // The quantized form has no in-place update: derive it again from the refitted
         // nodes through the bind-time host path (synchronous and slow; mrt.h).
+        // (Should a box no longer quantize, the exact form comes back and the commit puts its
+        // source map on the device beside the plan.)
         MRT_HIP(hipStreamSynchronize(s));
-        wide.builtFor = -1;
-        if (int rc = mrt::refresh_wide(t)) return rc;
-        // the exact form as a fallback would need a new source map on the device
-        if (wide.format == mrt::kNodeWide4) {
-            plan.built = false;
-            return mrt::build_plan(t);
-        }
+        return mrt::refresh_wide(t, true);
     }
     return MRT_OK;
 }
@@ -184,7 +149,7 @@ int mrt_tracer_refit_info(mrt_tracer* t, mrt_refit_info* info) {
     MRT_HIP(hipMemset(t->plan.skipped.get(), 0, sizeof(skipped)));
     info->levels = (int32_t)t->plan.levels.size() - 1;
     info->launches = t->plan.launches;
-    info->plan_bytes = t->plan.bytes;
+    info->plan_bytes = t->plan.bytes + t->wide.srcBytes();
     info->skipped_refs = (int64_t)skipped;
     return MRT_OK;
 }

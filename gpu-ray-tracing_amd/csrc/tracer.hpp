@@ -1,9 +1,12 @@
 // tracer.hpp — the tracer handle behind include/mrt.h and the functions of one C-ABI file that
 // another one calls. The handle's sub-objects own their device memory and events; each file
 // works on its own: the handle's lifecycle, configuration, workspace pool, tune events and the
-// trace path (mrt_api.cpp), bind and the 4-wide derivation (bind_api.cpp), refit (refit_api.cpp),
-// the device build (build_api.cpp), the plan and the 4-wide array derived on the device
-// (derive_api.cpp), the treelet restructuring (optimize_api.cpp).
+// trace path (mrt_api.cpp), refit (refit_api.cpp), the device build (build_api.cpp), the plan and
+// the 4-wide array derived on the device (derive_api.cpp), the treelet restructuring
+// (optimize_api.cpp). What a tracer holds of a bound tree (the borrowed buffers, the wide array
+// with its source map, the refit plan) has one writer, bind_api.cpp's commit: a bind and an
+// unbind replace all of it, set_config the plan, the schedules and (where cfg.wide changed) the
+// wide array, optimize all but the schedules, the first refit only the plan.
 #pragma once
 #include <chrono>
 #include <cstdint>
@@ -18,8 +21,22 @@
 
 namespace mrt {
 
-// 4-wide nodes derived from the bound Compact2 tree (cfg.wide; wide_bvh.cpp), owned by the
-// tracer and rebuilt when the BVH or the setting changes (refresh_wide).
+// The bound Compact2 BVH: device pointers borrowed from the caller. The extern "C" functions
+// build one from their arguments; a tracer that holds none (nodes null) is unbound.
+struct BvhBuffers {
+    const void* nodes = nullptr;
+    int64_t nodeBytes = 0;
+    const void* woop = nullptr;
+    int64_t woopBytes = 0;
+    const int32_t* triIndex = nullptr;
+    int64_t triIndexBytes = 0;
+    explicit operator bool() const { return nodes != nullptr; }
+    int64_t numNodes() const { return nodeBytes / 64; }
+};
+
+// 4-wide nodes derived from the bound Compact2 tree (cfg.wide), owned by the tracer: made by
+// install (a bind: the host collapse of wide_bvh.cpp, or derive_api.cpp on the device) or by
+// refresh_wide (set_config changed cfg.wide; the quantized form after a refit), dropped by unbind.
 struct WideArray {
     DeviceBuf<uint32_t> nodes;
     int64_t bytes = 0;
@@ -33,26 +50,28 @@ struct WideArray {
     // order; sized this way no ray of the bound tree can overflow it.
     int stackCap = kStackCapacity;
     int stackBound = kStackCapacity - 1;   // wide_stack_bound of the derived tree (the tail's headroom)
-    // Exact form only: per wide child the Compact2 slot (binary node * 2 + side) its box was
-    // copied from, -1 = absent — from the collapse that produced `nodes` (a refit copies the
-    // refitted boxes along it; collapsing refitted nodes again would choose other children).
-    std::vector<int32_t> src;
-    // The same map where the array was derived on the device (derive_api.cpp): it lives only
-    // there, `src` stays empty, and a refit reads it in place of the plan's copy.
-    DeviceBuf<int32_t> srcDev;
+    // Exact form only, the source map: per wide child the Compact2 slot (binary node * 2 + side)
+    // its box was copied from, -1 = absent — from the collapse that produced `nodes` (a refit
+    // copies the refitted boxes along it; collapsing refitted nodes again would choose other
+    // children). Its one home is the device, with the array it belongs to: the device derivation
+    // writes it there; the host collapse leaves it in srcHost until the tracer holds a refit plan
+    // (commit uploads it then and releases srcHost), so a tracer that never refits pays nothing.
+    DeviceBuf<int32_t> src;
+    std::vector<int32_t> srcHost;
+    int64_t srcBytes() const { return src ? bytes / 128 * 16 : 0; }
 };
 
 // Largest wide-traversal stack a tracer sizes its spill slab for (entries per lane).
 constexpr int kMaxWideStack = 1024;
 
-// The refit plan (mrt_tracer_refit), built on the first refit after a bind or set_config
-// and dropped by bind, unbind and set_config (drop_plan): the nodes by height level, the wide
-// source map and the refit's scratch, on the device.
+// The refit plan (mrt_tracer_refit): the nodes by height level and the refit's scratch, on the
+// device. Installed by a device bind, build or optimize, else by the first refit after a bind or
+// set_config; dropped by bind, unbind and set_config. The wide source map is not part of it
+// (WideArray::src); mrt_refit_info.plan_bytes counts both.
 struct RefitPlan {
     bool built = false;
     DeviceBuf<int32_t> order;      // numNodes node indices, level by level
     DeviceBuf<int32_t> offsets;    // levels + 1 offsets into order
-    DeviceBuf<int32_t> wideSrc;    // WideArray::src on the device (null: no exact wide array, or WideArray::srcDev)
     DeviceBuf<uint8_t> valid;      // 2 per node, rewritten by every refit
     DeviceBuf<unsigned long long> skipped;   // out-of-range references skipped since the last refit_info
     std::vector<int64_t> levels;   // the level offsets on the host
@@ -89,7 +108,24 @@ struct DeriveRun {
     Event ev[5];                     // topology begin / end, collapse begin, emission begin / end
     StreamScratch scratch;           // last: freed on its stream before the events go
 };
-enum : int { kDeriveOk = 0, kDeriveMalformed = 1, kDeriveTooDeep = 2 };
+
+// What derive() yields: the run, the plan it filled, or tooDeep (more than MRT_DERIVE_MAX_LEVELS
+// depth levels: no plan, the caller takes the host path).
+struct Derivation {
+    DeriveRun run;
+    RefitPlan plan;
+    bool tooDeep = false;
+};
+
+// What commit() puts in place of what the tracer holds; a null part stays as it is.
+struct Install {
+    WideArray* wide = nullptr;
+    RefitPlan* plan = nullptr;
+    const mrt_derive_info* derive = nullptr;   // lastDerive (wall_ms: the time since `since`)
+    const std::chrono::steady_clock::time_point* since = nullptr;   // with `wide`: bindMs
+    bool keepTunes = false;
+};
+enum : unsigned { kKeepTunes = 1, kUnbindOnError = 2 };   // install()'s flags
 
 // The event pairs of a TuneState's timing slots (created lazily, destroyed in tune_reset).
 struct TuneEvents {
@@ -110,22 +146,15 @@ struct mrt_tracer {
     int ldsPerBlock = 0;   // most LDS bytes one workgroup may hold
     std::mutex mu;
 
-    // Bound Compact2 BVH (borrowed device pointers).
-    bool bound = false;
-    const void* nodes = nullptr;
-    int64_t nodeBytes = 0;
-    const void* woop = nullptr;
-    int64_t woopBytes = 0;
-    const int32_t* triIndex = nullptr;
-    int64_t triIndexBytes = 0;
-
     mrt_launch_cfg cfg{};
 
+    // The bound tree and what is derived from it. commit() (bind_api.cpp) is their only writer.
+    mrt::BvhBuffers bvh;
     mrt::WideArray wide;
-    double bindMs = 0.0;               // wall time of the last bind / wide derivation (mrt_trace_info)
     mrt::RefitPlan plan;
-    mrt_build_info lastBuild{};        // the last successful mrt_tracer_build (mrt_tracer_build_info)
+    double bindMs = 0.0;               // wall time of the last bind / wide derivation (mrt_trace_info)
     mrt_derive_info lastDerive{};      // the last device bind / build / plan (mrt_tracer_derive_info)
+    mrt_build_info lastBuild{};        // the last successful mrt_tracer_build (mrt_tracer_build_info)
     mrt_optimize_info lastOptimize{};  // the last successful mrt_tracer_optimize (mrt_tracer_optimize_info)
 
     // Launch scratch, one set per stream the handle has launched on: the stack
@@ -161,36 +190,68 @@ namespace mrt {
 int wait_all_workspaces(mrt_tracer* t);
 void tune_reset(mrt_tracer* t);
 
-// bind_api.cpp: the bind itself, arguments checked (mrt_tracer_bind, mrt_tracer_build), and the
-// 4-wide nodes (re)derived when cfg.wide or the bound BVH asks for another array than the one held.
-int bind_locked(mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
-                const int32_t* triIndex, int64_t triIndexBytes);
-int refresh_wide(mrt_tracer* t);
-int check_bind_args(const mrt_tracer* t, const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,
-                    const int32_t* triIndex, int64_t triIndexBytes);
-void unbind_locked(mrt_tracer* t);
+// bind_api.cpp. check_bind_args: mrt_tracer_bind's and mrt_tracer_bind_device's argument checks.
+//
+// commit: the one writer of t->bvh, wide, plan, bindMs and lastDerive. It first does what can
+// fail (the source map goes to the device once a plan is held; this handle's traces, which read
+// the wide array, and its refit, which writes it and reads the plan, have finished), then
+// replaces, then forgets the tuned schedules unless told to keep them. On an error the tracer
+// holds what it held; only an unbind (b empty) goes through whatever the waits said.
+//
+// install: a bind. Makes the wide array cfg.wide asks for (d with a plan and cfg.wide 1: on the
+// device, enqueued on s, returning after the device has finished; else the host collapse) and
+// commits it with b and d's plan (d null: the host route, no plan, lastDerive stays; d->tooDeep:
+// the same, and lastDerive says so). since: the start of what bindMs counts (null: now).
+// kUnbindOnError: the caller has written the buffers, or promises it (mrt_tracer_bind_device).
+// unbind_locked is the install of nothing.
+//
+// refresh_wide: the host collapse again where set_config changed what cfg.wide asks for (the plan
+// and the schedules go in any case), or afterRefit for the quantized form, which has no
+// in-place update (plan and schedules stay). A collapse that fails leaves no array held.
+int check_bind_args(const mrt_tracer* t, const BvhBuffers& b);
+int commit(mrt_tracer* t, const BvhBuffers& b, const Install& in);
+int install(mrt_tracer* t, const BvhBuffers& b, Derivation* d, hipStream_t s, unsigned flags,
+            const std::chrono::steady_clock::time_point* since = nullptr);
+int unbind_locked(mrt_tracer* t);
+int refresh_wide(mrt_tracer* t, bool afterRefit);
+
+// The levels 1 .. of a plan's host offsets, lowest first: level(begin, count) per level above
+// tailNodes nodes, then tail(firstLevel, numLevels) once, in one workgroup, for all smaller ones
+// (level sizes never grow with the height). Both return a hipError_t; *launches counts them.
+template <class Level, class Tail>
+int walk_levels(const std::vector<int64_t>& offsets, int tailNodes, int* launches, Level level, Tail tail) {
+    const int levels = (int)offsets.size() - 1;
+    for (int l = 1; l < levels; l++) {
+        const int begin = (int)offsets[(size_t)l], count = (int)(offsets[(size_t)l + 1] - begin);
+        const bool rest = count <= tailNodes;
+        MRT_HIP(rest ? tail(l, levels) : level(begin, count));
+        ++*launches;
+        if (rest) break;
+    }
+    return MRT_OK;
+}
 
 // refit_api.cpp: waits for a refit that may still run (it reads the plan and writes the wide
-// array); forgets the plan; the refit's launches on Compact2 buffers, bound or not.
+// array); the refit's launches on Compact2 buffers, bound or not. The level plan made on the
+// host, for a host build or a tree above MRT_DERIVE_MAX_LEVELS depth levels: host_levels brings
+// the records to the host (a tree that is none: `code` with `prefix` + the reason),
+// upload_levels writes order, offsets (levels + 1) and a cleared skipped counter into the
+// caller's device buffers and returns after the copies.
+struct RefitLevels;
 int wait_refit(mrt_tracer* t);
-void drop_plan(mrt_tracer* t);
 int enqueue_refit(const RefitArgs& a, const std::vector<int64_t>& levelOffsets, const int32_t* order,
                   const int32_t* offsets, hipStream_t s, int* launches);
+int host_levels(const void* nodes, int64_t numNodes, hipStream_t s, int code, const char* prefix, RefitLevels* lv);
+int upload_levels(const RefitLevels& lv, int32_t* order, int32_t* offsets, unsigned long long* skipped, hipStream_t s);
 
 // derive_api.cpp: the refit plan and the exact 4-wide array derived on the device (wide_kernel.hip).
-// derive_begin takes the scratch for `numNodes` records at `nodes`; derive_plan fills p (order,
-// offsets, levels, valid, skipped; not wideSrc, not built) and sets *status: kDeriveMalformed
-// with *why = refit_levels' reason, kDeriveTooDeep above MRT_DERIVE_MAX_LEVELS depth levels (the
-// caller takes the host path). bind_derived is bind_locked for a tree whose plan p was derived
-// by r: the bookkeeping, the wide array per cfg.wide, the plan installed (keepTunes: the same
-// buffers re-installed by optimize_api.cpp, the tuned schedules stay). All enqueue on s;
-// bind_derived returns after the device has finished. derive_report fills t->lastDerive.
-int derive_begin(DeriveRun& r, const void* nodes, int64_t numNodes, hipStream_t s);
-int derive_plan(DeriveRun& r, RefitPlan* p, hipStream_t s, int* status, const char** why);
-int bind_derived(mrt_tracer* t, DeriveRun& r, RefitPlan&& p, const void* nodes, int64_t nodeBytes, const void* woop,
-                 int64_t woopBytes, const int32_t* triIndex, int64_t triIndexBytes, hipStream_t s, bool keepTunes = false);
-int derive_report(mrt_tracer* t, const DeriveRun& r, bool plan, bool wide, double wallMs);
-// The source map a refit of the exact wide array reads: the plan's copy or the wide array's own.
-const int32_t* refit_wide_src(const mrt_tracer* t);
+// derive: the plan of `numNodes` records at `nodes` into d (order, offsets, levels, valid,
+// skipped; not built), enqueued on s with a few waits; a tree that is none fails with `code` and
+// `prefix` + refit_levels' reason. derive_wide: the exact array of d's tree, its boxes final,
+// into w (no array where the stack bound is above kMaxWideStack). derive_report: what
+// mrt_tracer_derive_info says of d's run (not wall_ms), once s has finished.
+int derive(Derivation& d, const void* nodes, int64_t numNodes, hipStream_t s, int code, const char* prefix);
+int derive_wide(DeriveRun& r, const BvhBuffers& b, WideArray* w, hipStream_t s);
+int derive_report(const DeriveRun& r, bool plan, bool wide, mrt_derive_info* info);
 
 }  // namespace mrt

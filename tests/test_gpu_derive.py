@@ -8,11 +8,18 @@ trees only: trees that are none are refused on the CPU (tests/test_wide_plan.py)
   * the plan is installed by the bind or build itself, and a refit through it equals the host refit;
   * traces after a device bind equal the oracle at wide 0, 1 and, through the reported host
     fallback, 2; a second device bind rebinds; set_config re-derives the host's array;
-  * derive_info reports both parts on the device and far fewer readbacks than nodes.
+  * derive_info reports both parts on the device and far fewer readbacks than nodes;
+  * a tree of more than MRT_DERIVE_MAX_LEVELS depth levels goes through the host path in a device
+    bind and in the first refit, with the host's results, and the info says so;
+  * a device bind that refuses its tree leaves the tracer unbound, and a good bind follows;
+  * the source map of a host bind goes to the device once, and stays over a set_config that keeps
+    cfg.wide.
 
 scene_complete(12) has depth levels of 1 .. 2048 nodes: levels 0-10 run chained in one workgroup,
 level 11 (2048 nodes, above the 1024-node threshold) in a launch of its own.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -24,6 +31,8 @@ import kat  # noqa: E402
 import lbvh_util as L  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import refit_util as R  # noqa: E402
+import test_wide_plan as WP  # noqa: E402
+from mrt import _lib  # noqa: E402
 from mrt.tracer import GpuBvh, RayBuffer, Tracer, refit_plan  # noqa: E402
 
 ALPHA = 1e-5
@@ -247,6 +256,117 @@ def test_set_config_that_keeps_wide_keeps_the_device_array_and_its_map(tracer):
     torch.cuda.synchronize()
     same_plan(tracer.refit_plan(), plan)
     R.check_wide(wide, tracer.wide_nodes(), bufs[0], g.nodes.cpu().numpy())
+
+
+def test_the_source_map_of_a_host_bind_is_uploaded_once(tracer):
+    """The host-bound route of the test above: the first plan takes the map to the device, where
+    it stays with its array when set_config drops the plan."""
+    v, t, bufs, _ = R.built("random", 1500, ALPHA)
+    _, wide, _, plan = host_side(tracer, "random1500")
+    tracer.set_config(wide=1)
+    g = gpu(bufs)
+    tracer.set_bvh(g)
+    v2 = R.displaced(v)
+    tracer.refit(v2, t)
+    first_bytes, first_plan = tracer.refit_info()["plan_bytes"], tracer.refit_plan()
+    same_plan(first_plan, plan)
+    assert first_bytes == len(plan[0]) * 4 + len(plan[1]) * 4 + len(plan[0]) * 2 + 8 + plan[2].size * 4
+    tracer.set_config(spec_slack=tracer.config()["spec_slack"])   # drops the plan, keeps the array and its map
+    assert tracer.refit_plan() is None
+    tracer.refit(v2, t)
+    torch.cuda.synchronize()
+    assert tracer.refit_info()["plan_bytes"] == first_bytes
+    same_plan(tracer.refit_plan(), first_plan)
+    R.check_wide(wide, tracer.wide_nodes(), bufs[0], g.nodes.cpu().numpy())
+
+
+# ---- above MRT_DERIVE_MAX_LEVELS depth levels: the host path ----------------------------------------
+_CHAIN = []
+
+
+def deep_chain():
+    """(vertices, triangles, buffers) of a chain of 1100 records, boxes fitted: more depth levels
+    than the device derivation takes."""
+    if not _CHAIN:
+        import test_gpu_refit as TR
+        verts, tris, bufs = TR.chain_tree(_lib.MRT_DERIVE_MAX_LEVELS + 76, np.random.default_rng(9))
+        _CHAIN.append((verts, tris, tuple(R.host_refit(bufs, verts, tris))))
+    return _CHAIN[0]
+
+
+@pytest.mark.parametrize("wide", [1, 0])
+def test_device_bind_of_a_tree_too_deep_is_the_host_bind(tracer, wide):
+    _, _, bufs = deep_chain()
+    tracer.set_config(wide=wide)
+    tracer.set_bvh(gpu(bufs))
+    want, info = tracer.wide_nodes(), tracer.bind_info()   # with or without an array: the stack bound decides
+    tracer.set_bvh(gpu(bufs), on_device=True)
+    d = tracer.derive_info()
+    assert d["on_device_plan"] == 0 and d["on_device_wide"] == 0
+    got = tracer.wide_nodes()
+    assert got.size == want.size and R.same_bits_or_nan(got, want)
+    assert same_info(tracer.bind_info(), info)
+    assert tracer.refit_plan() is None
+    tracer.set_config(wide=1)
+
+
+@pytest.mark.parametrize("how", ["host", "device"])
+def test_first_refit_of_a_tree_too_deep_plans_on_the_host(tracer, how):
+    verts, tris, bufs = deep_chain()
+    tracer.set_config(wide=1)
+    g = gpu(bufs)
+    tracer.set_bvh(g, on_device=how == "device")
+    wide_before = tracer.wide_nodes()
+    v2 = R.displaced(verts)
+    want = R.host_refit(bufs, v2, tris)
+    tracer.refit(v2, tris)
+    torch.cuda.synchronize()
+    nodes, woop, tri = (x.cpu().numpy() for x in (g.nodes, g.woop, g.tri_index))
+    assert R.same_bits_or_nan(nodes, want[0]) and R.same_bits_or_nan(woop, want[1])
+    assert np.array_equal(tri, bufs[2])
+    order, offsets, src = refit_plan(bufs[0])
+    got = tracer.refit_plan()
+    assert got is not None and np.array_equal(got[0], order) and np.array_equal(got[1], offsets)
+    if wide_before.size:
+        assert got[2] is not None and np.array_equal(got[2], src)
+        R.check_wide(wide_before, tracer.wide_nodes(), bufs[0], nodes)
+    else:
+        assert got[2] is None
+    assert tracer.derive_info()["on_device_plan"] == 0
+    assert tracer.refit_info()["skipped_refs"] == 0
+
+
+# ---- a refused device bind --------------------------------------------------------------------------
+# test_wide_plan.malformed()'s cases whose child refs all stay inside the node array
+REFUSED = ["reached twice", "cycle to the root", "cycle to the parent", "unreachable", "one record, self cycle",
+           "two records, second unreachable"]
+
+
+def test_the_refused_cases_are_those_with_every_ref_inside_the_array():
+    assert sorted(REFUSED) == sorted(k for k, (_, why) in WP.malformed().items() if why in (WP.TWICE, WP.UNREACHED))
+
+
+@pytest.mark.parametrize("name", REFUSED)
+def test_a_refused_device_bind_leaves_the_tracer_unbound(tracer, name):
+    bufs, wide, info, plan = host_side(tracer, "random1500")
+    nodes, why = WP.malformed()[name]
+    tracer.set_config(wide=1)
+    tracer.set_bvh(gpu(bufs), on_device=True)
+    with pytest.raises(_lib.MrtError) as e:
+        tracer.set_bvh(gpu((nodes.reshape(-1), bufs[1], bufs[2])), on_device=True)
+    assert f"mrt error {_lib.MRT_ERR_INVALID_ARG} " in str(e.value)
+    assert str(e.value).endswith(why) and WP.host_reason(nodes).endswith(why)   # the host's reason
+    rb = RayBuffer(R.frame_rays(R.built("random", 1500, ALPHA)[0], 8, 8), need_closest_hit=True)
+    assert tracer.lib.mrt_tracer_trace(tracer._h, rb.rays.data_ptr(), rb.results.data_ptr(), rb.size, 0, None,
+                                       None) == _lib.MRT_ERR_NOT_BOUND
+    assert tracer.wide_nodes().size == 0
+    assert tracer.refit_info()["levels"] == 0
+    levels, nsrc = C.c_int32(-1), C.c_int64(-1)
+    assert tracer.lib.mrt_tracer_copy_refit_plan(tracer._h, None, None, 0, C.byref(levels), None, 0, C.byref(nsrc)) == 0
+    assert levels.value == 0 and nsrc.value == 0 and tracer.refit_plan() is None
+    tracer.set_bvh(gpu(bufs), on_device=True)
+    assert R.same_bits_or_nan(tracer.wide_nodes(), wide) and same_info(tracer.bind_info(), info)
+    same_plan(tracer.refit_plan(), plan)
 
 
 # ---- info -----------------------------------------------------------------------------------------
