@@ -1,6 +1,8 @@
 // compat_api.cpp — the implicit per-device tracers (mrt_bind_bvh / mrt_unbind_bvh /
 // mrt_trace) and the reference-compatible entry points of CudaTracerKernels.hh:42-52,
-// written against the public mrt_* functions of include/mrt.h only.
+// RayGenKernels.hh, RendererKernels.hh and RayBufferKernels.hh:112-117, written against the public
+// mrt_* functions of include/mrt.h (the three steps of the ray sort, which mrt_ray_sort runs as one
+// call, through raysort_kernel.hpp's launches).
 #include <climits>
 
 #include <cstdio>
@@ -8,6 +10,7 @@
 #include <mutex>
 
 #include "api_common.hpp"
+#include "raysort_kernel.hpp"
 
 using mrt::fail;
 using mrt::hipFail;
@@ -155,6 +158,62 @@ int32_t launch_countHitsKernel(int32_t threads, const int32_t* blockSize, mrt_co
     if (e != hipSuccess) compat_check(hipFail(e, "hipMemcpy"), __FILE__, __LINE__);
     if (f != hipSuccess) compat_check(hipFail(f, "hipFree"), __FILE__, __LINE__);
     return n;
+}
+
+// ---- RayBufferKernels.hh:112-117 (RayBuffer::mortonSort's three launches) ----
+
+void launch_findAABBKernel(int32_t nthreads, const int32_t* blockSize, mrt_find_aabb_input* in,
+                           mrt_find_aabb_output* out) {
+    (void)nthreads; (void)blockSize;   // launch shape of the reference (RayBuffer.cc:267-268)
+    if (!in || !out || in->numRays < 0 || in->numRays > mrt::raysort::kMaxRays || (in->numRays > 0 && !in->inRays))
+        compat_check(fail(MRT_ERR_INVALID_ARG, "bad FindAABBInput"), __FILE__, __LINE__);
+    if (in->numRays == 0) return;      // the reference's one block returns at once
+    mrt::DeviceBuf<float> scratch;     // the partials, then the box
+    hipError_t e = scratch.alloc((size_t)(mrt::kRaySortBoxBlocks + 1) * 6 * sizeof(float));
+    if (e != hipSuccess) compat_check(hipFail(e, "hipMalloc"), __FILE__, __LINE__);
+    float* box = scratch.get() + (size_t)mrt::kRaySortBoxBlocks * 6;
+    e = mrt::launch_raysort_box(static_cast<const uint4*>(in->inRays), in->numRays, 0, scratch.get(), box, nullptr);
+    if (e != hipSuccess) compat_check(hipFail(e, "find AABB launch"), __FILE__, __LINE__);
+    float got[6];
+    e = hipMemcpy(got, box, sizeof(got), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) compat_check(hipFail(e, "hipMemcpy"), __FILE__, __LINE__);
+    // the reference's atomicMin / atomicMax into the caller's box
+    mrt::raysort::Box all{{out->aabbLo[0], out->aabbLo[1], out->aabbLo[2]}, {out->aabbHi[0], out->aabbHi[1], out->aabbHi[2]}};
+    mrt::raysort::box_merge(all, mrt::raysort::Box{{got[0], got[1], got[2]}, {got[3], got[4], got[5]}});
+    for (int k = 0; k < 3; k++) {
+        out->aabbLo[k] = all.lo[k];
+        out->aabbHi[k] = all.hi[k];
+    }
+    e = hipDeviceSynchronize();
+    if (e != hipSuccess) compat_check(hipFail(e, "hipDeviceSynchronize"), __FILE__, __LINE__);
+}
+
+void launch_genMortonKeysKernel(int32_t nthreads, const int32_t* blockSize, mrt_gen_morton_keys_input* in) {
+    (void)nthreads; (void)blockSize;
+    if (!in || in->numRays < 0 || in->numRays > mrt::raysort::kMaxRays || (in->numRays > 0 && (!in->inRays || !in->outKeys)))
+        compat_check(fail(MRT_ERR_INVALID_ARG, "bad GenMortonKeysInput"), __FILE__, __LINE__);
+    if (in->numRays == 0) return;
+    static_assert(sizeof(mrt_morton_key) == 4 * (mrt::raysort::kKeyWords + 1), "MortonKey is oldSlot and six words");
+    const mrt::raysort::Box box{{in->aabbLo[0], in->aabbLo[1], in->aabbLo[2]}, {in->aabbHi[0], in->aabbHi[1], in->aabbHi[2]}};
+    hipError_t e = mrt::launch_raysort_keys(static_cast<const uint4*>(in->inRays), in->numRays, nullptr, box,
+                                            reinterpret_cast<uint32_t*>(in->outKeys), mrt::raysort::kKeyWords + 1, nullptr);
+    if (e != hipSuccess) compat_check(hipFail(e, "gen Morton keys launch"), __FILE__, __LINE__);
+    e = hipDeviceSynchronize();
+    if (e != hipSuccess) compat_check(hipFail(e, "hipDeviceSynchronize"), __FILE__, __LINE__);
+}
+
+void launch_reorderRaysKernel(int32_t nthreads, mrt_reorder_rays_input* in) {
+    (void)nthreads;
+    if (!in || in->numRays < 0 || in->numRays > mrt::raysort::kMaxRays ||
+        (in->numRays > 0 && (!in->inKeys || !in->inRays || !in->outRays)))
+        compat_check(fail(MRT_ERR_INVALID_ARG, "bad ReorderRaysInput"), __FILE__, __LINE__);
+    if (in->numRays == 0) return;
+    hipError_t e = mrt::launch_raysort_reorder(static_cast<const uint4*>(in->inRays), in->inSlotToID, in->numRays,
+                                               &in->inKeys->oldSlot, mrt::raysort::kKeyWords + 1,
+                                               static_cast<uint4*>(in->outRays), in->outIDToSlot, in->outSlotToID, nullptr);
+    if (e != hipSuccess) compat_check(hipFail(e, "reorder rays launch"), __FILE__, __LINE__);
+    e = hipDeviceSynchronize();
+    if (e != hipSuccess) compat_check(hipFail(e, "hipDeviceSynchronize"), __FILE__, __LINE__);
 }
 
 }  // extern "C"

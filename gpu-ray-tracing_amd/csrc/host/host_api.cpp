@@ -10,6 +10,7 @@
 #include "../../../include/mrt_host.h"
 #include "bvh.hpp"
 #include "fwhash.hpp"
+#include "host_error.hpp"
 #include "raygen.hpp"
 #include "scene.hpp"
 #include "treelet.hpp"
@@ -25,17 +26,11 @@ struct mrth_bvh {
 };
 
 namespace {
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
+int fail(int code, const std::string& msg) { return mrt::host_fail(code, msg); }
 mrt::Vec3f v3(const float* p) { return mrt::Vec3f(p[0], p[1], p[2]); }
 }  // namespace
 
 extern "C" {
-
-const char* mrth_last_error(void) { return g_err.c_str(); }
 
 int mrth_scene_synthetic(const char* name, int64_t param, uint64_t seed, mrth_scene** out) {
     if (!name || !out) return fail(MRTH_ERR_INVALID_ARG, "null argument");

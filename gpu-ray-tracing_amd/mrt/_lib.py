@@ -90,6 +90,37 @@ class OptimizeInfo(C.Structure):
                 ("device_ms", f32), ("wall_ms", C.c_double), ("scratch_bytes", i64)]
 
 
+class RaySortParams(C.Structure):
+    """mrt_ray_sort_params / mrth_ray_sort_params."""
+    _fields_ = [("drop_levels", i32), ("box", i32)]
+
+
+class MortonKey(C.Structure):
+    """RayBufferKernels.hh:46-50 (mrt.h mrt_morton_key)."""
+    _fields_ = [("oldSlot", i32), ("hash", u32 * 6)]
+
+
+class FindAABBInput(C.Structure):
+    """RayBufferKernels.hh:54-59 (mrt.h mrt_find_aabb_input)."""
+    _fields_ = [("numRays", i32), ("raysPerThread", i32), ("inRays", vp)]
+
+
+class FindAABBOutput(C.Structure):
+    """RayBufferKernels.hh:63-67 (mrt.h mrt_find_aabb_output)."""
+    _fields_ = [("aabbLo", f32 * 3), ("aabbHi", f32 * 3)]
+
+
+class GenMortonKeysInput(C.Structure):
+    """RayBufferKernels.hh:71-78 (mrt.h mrt_gen_morton_keys_input)."""
+    _fields_ = [("numRays", i32), ("aabbLo", f32 * 3), ("aabbHi", f32 * 3), ("inRays", vp), ("outKeys", vp)]
+
+
+class ReorderRaysInput(C.Structure):
+    """RayBufferKernels.hh:82-91 (mrt.h mrt_reorder_rays_input)."""
+    _fields_ = [("numRays", i32), ("inKeys", vp), ("inRays", vp), ("inSlotToID", vp), ("outRays", vp),
+                ("outIDToSlot", vp), ("outSlotToID", vp)]
+
+
 class TunedSchedule(C.Structure):
     _fields_ = [("num_rays", i32), ("variant", i32), ("candidate", i32), ("version", i32)]
 
@@ -157,6 +188,7 @@ TRACE_SYMBOLS = [
     ("mrt_raygen_ao", i32, [vp, vp, i32, vp, i64, i32, f32, u32, vp, vp, vp, vp]),
     ("mrt_raygen_ao_blocks", i32, [vp, vp, i32, vp, i64, i32, f32, vp, i32, i32, vp, i32, i32, i64, vp, vp]),
     ("mrt_shard_blocks", i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(i32), C.POINTER(i64), vp]),
+    ("mrt_ray_sort", i32, [vp, vp, i32, C.POINTER(RaySortParams), vp, vp, vp, vp, vp, vp]),
     ("mrt_count_hits", i32, [vp, i32, vp, vp]),
     ("mrt_reconstruct", i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     ("mrt_selftest_exact_rcp", i32, [C.POINTER(C.c_uint64)]),
@@ -168,6 +200,9 @@ TRACE_SYMBOLS = [
     ("launch_rayGenPrimaryKernel", None, [i32, vp]),
     ("launch_rayGenAOKernel", None, [i32, vp]),
     ("launch_countHitsKernel", i32, [i32, vp, vp]),
+    ("launch_findAABBKernel", None, [i32, vp, C.POINTER(FindAABBInput), C.POINTER(FindAABBOutput)]),
+    ("launch_genMortonKeysKernel", None, [i32, vp, C.POINTER(GenMortonKeysInput)]),
+    ("launch_reorderRaysKernel", None, [i32, C.POINTER(ReorderRaysInput)]),
 ]
 
 # (name, restype, argtypes) of every symbol include/mrt_host.h declares.
@@ -204,6 +239,7 @@ HOST_SYMBOLS = [
     ("mrth_camera_decode_signature", i32, [C.c_char_p, C.POINTER(HostCamera), C.POINTER(f32), C.POINTER(i32)]),
     ("mrth_ao_rays", i32, [vp, vp, i64, vp, i32, f32, u32, vp]),
     ("mrth_count_hits", i64, [vp, i64]),
+    ("mrth_ray_sort", i32, [vp, vp, i32, C.POINTER(RaySortParams), vp, vp, vp, vp, vp]),
     ("mrth_last_error", C.c_char_p, []),
 ]
 

@@ -292,6 +292,28 @@ def count_hits(results: np.ndarray) -> int:
     return int(_lib.host_lib().mrth_count_hits(_ptr(r), len(r)))
 
 
+def ray_sort(rays, slot_to_id=None, drop_levels: int = 0, box: int = 0) -> dict:
+    """RayBuffer::mortonSort on the host (mrth_ray_sort; the CPU statement of
+    RayBuffer.morton_sort, whose bits it reproduces): the batch in the order of the reference's
+    Morton key >> (6 * drop_levels), ties by input slot. box 0 takes the key's box over origins
+    and end points (the reference), 1 over origins only. Returns numpy arrays: rays float32
+    [n, 8], id_to_slot and slot_to_id int32 [n] (id_to_slot starts at -1: an id outside [0, n)
+    writes no entry), keys uint32 [n, 6] in INPUT order, box float32 [6] (lo.xyz, hi.xyz)."""
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    n = len(r)
+    s2i = None if slot_to_id is None else np.ascontiguousarray(slot_to_id, np.int32)
+    if s2i is not None and s2i.shape != (n,):
+        raise _lib.MrtError("slot_to_id must hold one id per ray")
+    out = {"rays": np.zeros((n, 8), np.float32), "id_to_slot": np.full(n, -1, np.int32),
+           "slot_to_id": np.zeros(n, np.int32), "keys": np.zeros((n, 6), np.uint32), "box": np.zeros(6, np.float32)}
+    params = _lib.RaySortParams(drop_levels=int(drop_levels), box=int(box))
+    _lib.check_host(_lib.host_lib().mrth_ray_sort(_ptr(r) if n else None, None if s2i is None else _ptr(s2i), n,
+                                                  C.byref(params), _ptr(out["rays"]) if n else None,
+                                                  _ptr(out["id_to_slot"]), _ptr(out["slot_to_id"]),
+                                                  _ptr(out["keys"]), _ptr(out["box"])))
+    return out
+
+
 def write_ppm(path: str, pixels: np.ndarray, w: int, h: int, flip: bool = True) -> None:
     """Binary PPM (P6) of w*h ABGR uint32 pixels indexed y*w + x (the reference's
     PBO, Renderer.cc:221-238). flip=True writes row h-1 first: the reference drew

@@ -7,7 +7,10 @@ and RayGen's batching (src/rt/ray/RayGen.cc:77-142) over the C-ABI.
   nextBatch       Renderer.cc:242-291   the next <= maxBatchSize rays (RayGen::batching,
                                         RayGen.cc:124-142): primaries [lo, hi) with
                                         hi = min(n, lo + maxBatch / numSamples), numSamples rays each,
-                                        seeded by the next glibc rand() (RayGen.cc:106)
+                                        seeded by the next glibc rand() (RayGen.cc:106); with
+                                        sortSecondary (Renderer.hh:67, Renderer.cc:287-288; off by
+                                        default, as the reference's App leaves it) an AO / diffuse
+                                        batch is then Morton-sorted (RayBuffer.morton_sort)
   traceBatch      Renderer.cc:295-300   CudaTracer::traceBatch of the current batch -> ms
   updateResult    Renderer.cc:421-445   reconstructKernel of the batch into the frame's pixels
 
@@ -83,11 +86,19 @@ class Renderer:
         self._next_input = 0      # RayGen's m_aoStartIdx
         self._new_batch = True
         self._seeds: list[int] = []   # this frame's batch seeds, drawn from rand() in batch order
+        self.sort_secondary, self.sort_drop_levels, self.sort_box = False, 0, 0
+        self.batch_id_to_slot: torch.Tensor | None = None   # of a sorted batch; None = the identity layout
 
-    def set_params(self, ray_type: int = RAY_PRIMARY, num_samples: int = 1, ao_radius: float = 5.0) -> None:
+    def set_params(self, ray_type: int = RAY_PRIMARY, num_samples: int = 1, ao_radius: float = 5.0,
+                   sort_secondary: bool = False, sort_drop_levels: int = 0, sort_box: int = 0) -> None:
+        """sort_secondary: Morton-sort every AO / diffuse batch before it is traced (the reference's
+        sortSecondary); sort_drop_levels / sort_box: RayBuffer.morton_sort's drop_levels and box."""
         if ray_type not in (RAY_PRIMARY, RAY_AO, RAY_DIFFUSE):
             raise _lib.MrtError(f"unknown ray type {ray_type}")
+        if not 0 <= int(sort_drop_levels) <= 24 or int(sort_box) not in (0, 1):
+            raise _lib.MrtError(f"sort_drop_levels {sort_drop_levels} outside 0..24 or sort_box {sort_box} outside 0..1")
         self.ray_type, self.num_samples, self.ao_radius = ray_type, int(num_samples), float(ao_radius)
+        self.sort_secondary, self.sort_drop_levels, self.sort_box = bool(sort_secondary), int(sort_drop_levels), int(sort_box)
 
     def begin_frame(self, cam: Camera, w: int, h: int, subpixel=(0.5, 0.5)) -> None:
         self.cam, self.w, self.h = cam, w, h
@@ -95,6 +106,7 @@ class Renderer:
         if self.ray_type != RAY_PRIMARY:
             self.tracer.trace_batch(self.primary, exact_rcp=self.exact_rcp)
         self.batch, self.batch_start, self._next_input, self._new_batch = None, 0, 0, True
+        self.batch_id_to_slot = None
         self._seeds = []
 
     def total_num_rays(self) -> int:
@@ -106,6 +118,7 @@ class Renderer:
         if self.batch is not None:
             self.batch_start += self.batch.size
         self.batch = None
+        self.batch_id_to_slot = None
         if self.ray_type == RAY_PRIMARY:
             if not self._new_batch:
                 return False
@@ -120,6 +133,9 @@ class Renderer:
         self.batch = self.gen.ao(self.primary, self.num_samples, self._max_dist(),
                                  seed=self.batch_seeds(lo // self._batch_inputs() + 1)[-1],
                                  closest_hit=self.ray_type == RAY_DIFFUSE, first=lo, count=hi - lo)
+        if self.sort_secondary:    # Renderer.cc:287-288
+            self.batch, self.batch_id_to_slot, _ = self.batch.morton_sort(drop_levels=self.sort_drop_levels,
+                                                                          box=self.sort_box)
         return True
 
     def _max_dist(self) -> float:
@@ -179,7 +195,8 @@ class Renderer:
             self._recon = DeviceReconstructor(self.scene)
         n = 1 if self.ray_type == RAY_PRIMARY else self.num_samples
         return self._recon.reconstruct(self.ray_type, self.primary, self.slot_to_id, self.w * self.h, self.batch,
-                                       num_samples=n, pixels=pixels, first_primary=self.batch_start // n)
+                                       num_samples=n, pixels=pixels, first_primary=self.batch_start // n,
+                                       batch_id_to_slot=self.batch_id_to_slot)
 
     def batches(self):
         """Every batch of the frame (generated, not traced) as (RayBuffer, first ray) pairs."""

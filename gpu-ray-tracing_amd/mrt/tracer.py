@@ -90,6 +90,39 @@ class RayBuffer:
         return RayBuffer(self.rays[lo:hi], self.need_closest_hit, self.rays.device, self.results[lo:hi],
                          secondary=self.secondary)
 
+    def morton_sort(self, slot_to_id: torch.Tensor | None = None, drop_levels: int = 0, box: int = 0, stream=None,
+                    want_keys: bool = False):
+        """RayBuffer::mortonSort (RayBuffer.cc:256-324) on the device, stream-ordered with no host
+        sync (mrt_ray_sort): a new RayBuffer of this one's rays in the order of the reference's
+        Morton key >> (6 * drop_levels), ties by slot; box 0 takes the key's box over origins and
+        end points (the reference), 1 over origins only. slot_to_id: this buffer's int32 ids
+        (None = the identity). Returns (sorted RayBuffer, id_to_slot, slot_to_id) — id_to_slot
+        starts at -1 and is what reconstruct takes as batch_id_to_slot — and, with want_keys,
+        also keys (uint32 bits as int32 [n, 6], in this buffer's order) and box (float32 [6]).
+        The new buffer keeps need_closest_hit and secondary and has fresh results."""
+        dev = self.rays.device
+        n = self.size
+        if dev.type != "cuda":
+            raise _lib.MrtError("morton_sort needs rays on a HIP device (mrt.host.ray_sort sorts host rays)")
+        if slot_to_id is not None and (slot_to_id.dtype != torch.int32 or tuple(slot_to_id.shape) != (n,) or
+                                       slot_to_id.device != dev or not slot_to_id.is_contiguous()):
+            raise _lib.MrtError("morton_sort: slot_to_id must be a contiguous int32 [n] tensor on the rays' device")
+        out = torch.empty_like(self.rays)
+        id_to_slot = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        new_slot_to_id = torch.empty(n, dtype=torch.int32, device=dev)
+        keys = torch.empty((n, 6), dtype=torch.int32, device=dev) if want_keys else None
+        box_out = torch.empty(6, dtype=torch.float32, device=dev) if want_keys else None
+        params = _lib.RaySortParams(drop_levels=int(drop_levels), box=int(box))
+        _lib.check(_lib.trace_lib().mrt_ray_sort(
+            self.rays.data_ptr(), None if slot_to_id is None else slot_to_id.data_ptr(), n, C.byref(params),
+            out.data_ptr(), id_to_slot.data_ptr(), new_slot_to_id.data_ptr(),
+            None if keys is None else keys.data_ptr(), None if box_out is None else box_out.data_ptr(),
+            _stream_ptr(stream)))
+        rb = RayBuffer(out, self.need_closest_hit, dev, secondary=self.secondary)
+        if want_keys:
+            return rb, id_to_slot, new_slot_to_id, keys, box_out
+        return rb, id_to_slot, new_slot_to_id
+
     @property
     def size(self) -> int:
         return int(self.rays.shape[0])

@@ -704,6 +704,48 @@ int  mrt_shard_blocks(const void* primaryResults, int32_t numPrimary, int32_t nu
                       int32_t world, int32_t rank, int32_t order, int32_t* blocks, int32_t capacity,
                       int32_t* numBlocks, int64_t* numRays, void* stream);
 
+/* Parameters of mrt_ray_sort (NULL = defaults). */
+typedef struct mrt_ray_sort_params {
+    int32_t drop_levels;  /* 0..24, 0 = the reference's full key */
+    int32_t box;          /* 0 = origins and end points (reference), 1 = origins only */
+} mrt_ray_sort_params;
+
+/* RayBuffer::mortonSort (RayBuffer.cc:256-324; findAABBKernel, genMortonKeysKernel and
+ * reorderRaysKernel, RayBufferKernels.cu:74-200) without its two copies and its CPU sort: the
+ * batch is put in the order of the reference's Morton key on the device. perm being that order,
+ * outRays[j] = inRays[perm[j]] moved as bits, id = inSlotToId ? inSlotToId[perm[j]] : perm[j],
+ * outSlotToId[j] = id, and outIdToSlot[id] = j where 0 <= id < numRays (an id outside that range
+ * is never used as an index; the caller's contract, as in the reference, is a permutation).
+ * outIdToSlot is what mrt_reconstruct takes as batchIdToSlot for the sorted batch's results.
+ *   - The key (csrc/raysort_common.hpp; mrth_ray_sort, mrt_host.h, gives the same bits): the box
+ *     lo / hi starts at +-FLT_MAX and takes every origin o and, with box 0, every end point
+ *     o + d * tmax (a NaN never enters). Per axis a = (o - lo) / (hi - lo) and
+ *     b = (d / |d| + 1) / 2 in IEEE float32 (the reference compiles these under fast-math, so its
+ *     own bits are not defined), q = a * 2^24 capped at 2^24, r = b * 2^21 capped at 2^21, NaN and
+ *     negative to 0. Bit 6 i + c of the key is bit i of component c of q.x, q.y, q.z, r.x, r.y,
+ *     r.z (collectBits); six 32-bit words, word 5 most significant (0 with the caps).
+ *     box 1 leaves the end points out: a diffuse batch's tmax is the camera's far distance, and
+ *     its end points stretch the box until the origins share a few key levels.
+ *   - The order: ascending by key >> (6 * drop_levels), ties by ascending input slot. The
+ *     reference leaves ties to an unstable quicksort; a stable order is one of its outcomes and
+ *     does not vary between runs. drop_levels d leaves the bit levels i < d of all six components
+ *     out. The sort is LSD over the 64-bit words of the shifted key: three radix-sort passes for
+ *     d <= 3, two for d <= 14, one above, each over the bits that can be set.
+ *   - outKeys (may be NULL): six words per ray in INPUT order. outBox (may be NULL): lo.xyz,
+ *     hi.xyz in device memory; the sign of a zero there may differ from mrth_ray_sort's.
+ *   - Stream-ordered on `stream` (a hipStream_t, NULL = the null stream): no host sync and no
+ *     readback. Scratch (about 60 bytes per ray, 24 less with outKeys) is taken and returned on
+ *     the stream (hipMallocAsync / hipFreeAsync; a failed allocation is MRT_ERR_HIP).
+ * numRays == 0 returns MRT_OK and launches nothing. MRT_ERR_INVALID_ARG for a negative count, a
+ * null inRays or outRays, outRays overlapping inRays, or parameters out of range;
+ * MRT_ERR_TOO_LARGE above 2^30 rays. In these cases nothing is written.
+ * Whether the sort pays for itself is measured, not promised (tools/raysort_probe.py). */
+int  mrt_ray_sort(const void* inRays, const int32_t* inSlotToId /* NULL = identity */, int32_t numRays,
+                  const mrt_ray_sort_params* params /* NULL = defaults */, void* outRays,
+                  int32_t* outIdToSlot /* may be NULL */, int32_t* outSlotToId /* may be NULL */,
+                  uint32_t* outKeys /* may be NULL: 6 words per ray, in INPUT order */,
+                  float* outBox /* may be NULL: lo.xyz, hi.xyz, device */, void* stream);
+
 /* countHitsKernel (RendererKernels.cu:112-162): *hitCount (device int32) = number of
  * results with id >= 0. */
 int  mrt_count_hits(const void* results, int32_t numRays, int32_t* hitCount, void* stream);
@@ -810,6 +852,55 @@ void    launch_rayGenAOKernel(int32_t nthreads, mrt_raygen_ao_input* in);
 void    launch_reconstructKernel(int32_t nthreads, mrt_reconstruct_input* in);
 /* launch_countHitsKernel (RendererKernels.cu:189-215): returns the hit count */
 int32_t launch_countHitsKernel(int32_t threads, const int32_t* blockSize, mrt_count_hits_input* in);
+
+/* RayBufferKernels.hh:46-91 structs, field for field: Vec3f = 3 floats, then 8-byte-aligned
+ * pointers (device memory). What a reference build with Renderer's sortSecondary on needs at
+ * link time; mrt_ray_sort does the whole of RayBuffer::mortonSort without its two copies of the
+ * keys and its CPU sort. */
+typedef struct mrt_morton_key {
+    int32_t  oldSlot;
+    uint32_t hash[6];          /* hash[5] most significant */
+} mrt_morton_key;
+
+typedef struct mrt_find_aabb_input {
+    int32_t  numRays;
+    int32_t  raysPerThread;
+    void*    inRays;
+} mrt_find_aabb_input;
+
+typedef struct mrt_find_aabb_output {
+    float    aabbLo[3];
+    float    aabbHi[3];
+} mrt_find_aabb_output;
+
+typedef struct mrt_gen_morton_keys_input {
+    int32_t  numRays;
+    float    aabbLo[3];
+    float    aabbHi[3];
+    void*    inRays;
+    mrt_morton_key* outKeys;
+} mrt_gen_morton_keys_input;
+
+typedef struct mrt_reorder_rays_input {
+    int32_t  numRays;
+    mrt_morton_key* inKeys;
+    void*    inRays;
+    int32_t* inSlotToID;
+    void*    outRays;
+    int32_t* outIDToSlot;
+    int32_t* outSlotToID;
+} mrt_reorder_rays_input;
+
+/* launch_findAABBKernel / launch_genMortonKeysKernel / launch_reorderRaysKernel
+ * (RayBufferKernels.cu:204-255; prototypes RayBufferKernels.hh:112-117): blocking, the launch-shape
+ * arguments are ignored. findAABB folds the rays' box (origins and end points) into *out, a HOST
+ * struct the caller starts at +-FLT_MAX; genMortonKeys takes the box from *in and writes
+ * {oldSlot = index, key} per ray; reorderRays reads oldSlot from the (sorted) keys and moves
+ * rays and ids as mrt_ray_sort does (an oldSlot or id outside [0, numRays) is skipped). */
+void    launch_findAABBKernel(int32_t nthreads, const int32_t* blockSize, mrt_find_aabb_input* in,
+                              mrt_find_aabb_output* out);
+void    launch_genMortonKeysKernel(int32_t nthreads, const int32_t* blockSize, mrt_gen_morton_keys_input* in);
+void    launch_reorderRaysKernel(int32_t nthreads, mrt_reorder_rays_input* in);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,23 @@ int  mrth_ao_rays(const void* primaryRays, const void* primaryResults, int64_t n
                   void* outRays /* numPrimary * numSamples Ray */);
 int64_t mrth_count_hits(const void* results, int64_t n);
 
+/* RayBuffer::mortonSort (RayBuffer.cc:256-324): the CPU statement of mrt_ray_sort (mrt.h, which
+ * states the key and the order), with the same arguments over HOST memory and no stream. outBox
+ * is six host floats (lo.xyz, hi.xyz). The box and the keys are csrc/raysort_common.hpp's on both
+ * sides and the sort is std::stable_sort on key >> (6 * drop_levels), so keys, box values (up to
+ * the sign of a zero), permutation, rays and both id maps equal the device's bit for bit.
+ * MRTH_ERR_INVALID_ARG where mrt_ray_sort refuses (more than 2^30 rays included); numRays == 0
+ * returns MRTH_OK and writes nothing. */
+typedef struct mrth_ray_sort_params {
+    int32_t drop_levels;  /* 0..24, 0 = the reference's full key */
+    int32_t box;          /* 0 = origins and end points (reference), 1 = origins only */
+} mrth_ray_sort_params;
+int  mrth_ray_sort(const void* inRays, const int32_t* inSlotToId /* NULL = identity */, int32_t numRays,
+                   const mrth_ray_sort_params* params /* NULL = defaults */, void* outRays,
+                   int32_t* outIdToSlot /* may be NULL */, int32_t* outSlotToId /* may be NULL */,
+                   uint32_t* outKeys /* may be NULL: 6 words per ray, in INPUT order */,
+                   float* outBox /* may be NULL: lo.xyz, hi.xyz */);
+
 const char* mrth_last_error(void);
 
 #ifdef __cplusplus
