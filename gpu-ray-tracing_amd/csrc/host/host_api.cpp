@@ -13,7 +13,9 @@
 #include "host_error.hpp"
 #include "raygen.hpp"
 #include "scene.hpp"
+#include "scene_attr.hpp"
 #include "treelet.hpp"
+#include "../scene_common.hpp"
 
 static_assert(MRTH_OPTIMIZE_MAX_ROUNDS == mrt::kOptimizeMaxRounds, "mrt_host.h and treelet.hpp disagree");
 
@@ -83,40 +85,40 @@ int mrth_scene_copy_arrays(const mrth_scene* s, float* vertices, int32_t* triang
     return MRTH_OK;
 }
 
-namespace {
-// Vec4f::toABGR, host variant (reference Math.cc:45-52): clamp, scale by 2^56 in
-// double, times 255, round half up in fixed point. The clamp is the framework's
-// min(max(v, 0), 1) with max(a, b) = a > b ? a : b (Defs.hh:141-159), which sends a NaN
-// channel (the shade of a triangle whose normal overflowed) to 0, not through.
-uint32_t host_to_abgr(const float v[4]) {
-    uint32_t r = 0;
-    for (int i = 0; i < 4; i++) {
-        const float lo = v[i] > 0.0f ? v[i] : 0.0f;
-        const float c = lo < 1.0f ? lo : 1.0f;
-        const uint64_t q = (uint64_t)((double)c * 72057594037927936.0);   // exp2(56)
-        r |= (uint32_t)((((q * 255u) >> 55) + 1) >> 1) << (8 * i);
-    }
-    return r;
-}
-}  // namespace
-
 int mrth_scene_tri_colors(const mrth_scene* s, uint32_t* material, uint32_t* shaded) {
     if (!s) return fail(MRTH_ERR_INVALID_ARG, "null scene");
     // Scene::Scene (reference Scene.cc:37,68-80): each triangle's submesh material
-    // (OBJ .mtl Kd/d), or the default MeshBase::Material (Mesh.hh:92: diffuse (0.75, 0.75, 0.75, 1)).
-    static const float kDefault[4] = {0.75f, 0.75f, 0.75f, 1.0f};
-    const mrt::Vec3f light = mrt::normalize(mrt::Vec3f{1.0f, 2.0f, 3.0f});
+    // (OBJ .mtl Kd/d), or the default MeshBase::Material (Mesh.hh:92: diffuse (0.75, 0.75, 0.75, 1)),
+    // shaded and packed by scene_common.hpp's shade / to_abgr (the host Vec4f::toABGR).
+    float kDefault[4], light[3];
+    mrt::scene::default_diffuse(kDefault);
+    mrt::scene::light_dir(light);
     const size_t nt = s->scene.triNormals.size();
     const bool perTri = s->scene.triDiffuse.size() == 4 * nt;
     for (size_t i = 0; i < nt; i++) {
         const float* diffuse = perTri ? &s->scene.triDiffuse[4 * i] : kDefault;
-        if (material) material[i] = host_to_abgr(diffuse);
-        if (shaded) {
-            const float k = mrt::dot(s->scene.triNormals[i], light) * 0.5f + 0.5f;
-            const float c[4] = {diffuse[0] * k, diffuse[1] * k, diffuse[2] * k, 1.0f};
-            shaded[i] = host_to_abgr(c);
-        }
+        if (material) material[i] = mrt::scene::to_abgr(diffuse);
+        if (shaded) shaded[i] = mrt::scene::shade(&s->scene.triNormals[i].x, light, diffuse);
     }
+    return MRTH_OK;
+}
+
+int mrth_scene_tri_diffuse(const mrth_scene* s, float* out) {
+    if (!s || !out) return fail(MRTH_ERR_INVALID_ARG, "null argument");
+    const size_t nt = s->scene.triangles.size();
+    if (s->scene.triDiffuse.size() == 4 * nt) {
+        std::memcpy(out, s->scene.triDiffuse.data(), nt * 16);
+    } else {
+        for (size_t i = 0; i < nt; i++) mrt::scene::default_diffuse(out + 4 * i);
+    }
+    return MRTH_OK;
+}
+
+int mrth_bvh_tree_cost(const mrth_bvh* b, mrth_tree_cost* out) {
+    if (!b || !out) return fail(MRTH_ERR_INVALID_ARG, "null argument");
+    if (b->c2.nodes.size() < 16) return fail(MRTH_ERR_INVALID_ARG, "tree_cost: the tree has no record");
+    mrt::tree_cost(b->c2.nodes.data(), (int64_t)b->c2.nodes.size() / 16, b->c2.woop.data(),
+                   (int64_t)b->c2.woop.size() / 4, out);
     return MRTH_OK;
 }
 

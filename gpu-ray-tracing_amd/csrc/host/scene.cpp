@@ -10,6 +10,7 @@
 // dense foliage (san). Everything is derived from a splitmix64 stream and libm, so the
 // same binary produces bit-identical scenes on every host.
 #include "scene.hpp"
+#include "../scene_common.hpp"
 
 #include <algorithm>
 #include <array>
@@ -590,7 +591,7 @@ void Scene::compute_normals() {   // Scene.cc:66-75
     triNormals.resize(triangles.size());
     for (size_t i = 0; i < triangles.size(); i++) {
         const Vec3i& t = triangles[i];
-        triNormals[i] = normalize(cross(vertices[t.y] - vertices[t.x], vertices[t.z] - vertices[t.x]));
+        scene::tri_normal(&vertices[t.x].x, &vertices[t.y].x, &vertices[t.z].x, &triNormals[i].x);   // scene_common.hpp
     }
 }
 

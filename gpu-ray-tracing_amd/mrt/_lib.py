@@ -90,6 +90,12 @@ class OptimizeInfo(C.Structure):
                 ("device_ms", f32), ("wall_ms", C.c_double), ("scratch_bytes", i64)]
 
 
+class TreeCost(C.Structure):
+    """mrt_tree_cost / mrth_tree_cost."""
+    _fields_ = [("root_area", C.c_double), ("inner_area", C.c_double), ("leaf_area", C.c_double),
+                ("leaf_tri_area", C.c_double), ("records", i64), ("leaves", i64), ("triangles", i64), ("skipped", i64)]
+
+
 class RaySortParams(C.Structure):
     """mrt_ray_sort_params / mrth_ray_sort_params."""
     _fields_ = [("drop_levels", i32), ("box", i32)]
@@ -190,6 +196,8 @@ TRACE_SYMBOLS = [
     ("mrt_shard_blocks", i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(i32), C.POINTER(i64), vp]),
     ("mrt_ray_sort", i32, [vp, vp, i32, C.POINTER(RaySortParams), vp, vp, vp, vp, vp, vp]),
     ("mrt_count_hits", i32, [vp, i32, vp, vp]),
+    ("mrt_scene_attributes", i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
+    ("mrt_tracer_tree_cost", i32, [vp, C.POINTER(TreeCost), vp, vp]),
     ("mrt_reconstruct", i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     ("mrt_selftest_exact_rcp", i32, [C.POINTER(C.c_uint64)]),
     ("bind_CudaBVHTexture", None, [vp, i64, vp, i64, vp, i64]),
@@ -216,6 +224,9 @@ HOST_SYMBOLS = [
     ("mrth_scene_copy_arrays", i32, [vp, vp, vp, vp]),
     ("mrth_scene_camera", i32, [vp, C.POINTER(HostCamera), C.POINTER(f32)]),
     ("mrth_scene_tri_colors", i32, [vp, vp, vp]),
+    ("mrth_scene_tri_diffuse", i32, [vp, vp]),
+    ("mrth_scene_attributes", i32, [vp, i64, vp, i64, vp, vp, vp, vp, C.POINTER(i64)]),
+    ("mrth_bvh_tree_cost", i32, [vp, C.POINTER(TreeCost)]),
     ("mrth_default_build_params", None, [C.POINTER(BuildParams)]),
     ("mrth_fw_hash_buffer", u32, [vp, i64]),
     ("mrth_scene_hash", u32, [vp]),

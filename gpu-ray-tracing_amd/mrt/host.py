@@ -123,6 +123,13 @@ class Scene:
         _lib.check_host(_lib.host_lib().mrth_scene_tri_colors(self._h, _ptr(mat), _ptr(sh)))
         return mat, sh
 
+    def tri_diffuse(self) -> np.ndarray:
+        """Each triangle's material diffuse colour, float32 [nt, 4] (mrth_scene_tri_diffuse): the
+        OBJ's .mtl Kd / d, or the default (0.75, 0.75, 0.75, 1); scene_attributes' diffuse input."""
+        out = np.empty((self.num_triangles, 4), np.float32)
+        _lib.check_host(_lib.host_lib().mrth_scene_tri_diffuse(self._h, _ptr(out)))
+        return out
+
     def camera(self):
         c = _lib.HostCamera()
         ao = C.c_float()
@@ -244,10 +251,63 @@ class Bvh:
         return {"rounds": info.rounds, "levels": info.levels, "considered": list(info.considered[:info.rounds]),
                 "rewritten": list(info.rewritten[:info.rounds]), "wall_ms": info.wall_ms}
 
+    def tree_cost(self) -> dict:
+        """The tree's area sums (mrth_bvh_tree_cost; the CPU statement of Tracer.tree_cost) and
+        the SAH cost they give: see tree_cost_dict."""
+        c = _lib.TreeCost()
+        _lib.check_host(_lib.host_lib().mrth_bvh_tree_cost(self._h, C.byref(c)))
+        return tree_cost_dict(c)
+
     def stats(self) -> dict:
         s = _lib.BvhStats()
         _lib.check_host(_lib.host_lib().mrth_bvh_get_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in s._fields_}
+
+
+# The reference's default SAH costs of a node and of a triangle (Platform.hh:42-43: 1.f, 1.f).
+SAH_NODE_COST = 1.0
+SAH_TRIANGLE_COST = 1.0
+
+
+def tree_cost_dict(c: "_lib.TreeCost") -> dict:
+    """mrt_tree_cost's fields plus sah = (Cn * inner_area + Ct * leaf_tri_area) / root_area with
+    the reference's Platform defaults Cn = Ct = 1 (Platform.hh:42-43); None where root_area is 0."""
+    out = {k: getattr(c, k) for k, _ in c._fields_}
+    out["sah"] = ((SAH_NODE_COST * c.inner_area + SAH_TRIANGLE_COST * c.leaf_tri_area) / c.root_area
+                  if c.root_area > 0.0 else None)
+    return out
+
+
+def scene_attributes(vertices, triangles, diffuse=None, normals: bool = True, shaded: bool = True,
+                     material: bool = True) -> dict:
+    """A scene's per-triangle tables over plain arrays (mrth_scene_attributes; the CPU statement
+    of mrt_scene_attributes, whose bits it gives): normals float32 [nt, 3], shaded and material
+    ABGR uint32 [nt] (each only when asked for), and skipped, the triangles with a vertex index
+    outside the vertex array (normal (0, 0, 0)). diffuse: float32 [nt, 4], None = the default
+    material."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+    d = None if diffuse is None else np.ascontiguousarray(diffuse, np.float32).reshape(-1, 4)
+    if d is not None and len(d) != len(t):
+        raise _lib.MrtError("diffuse must hold 4 floats per triangle")
+    out = {}
+    if normals:
+        out["normals"] = np.zeros((len(t), 3), np.float32)
+    if shaded:
+        out["shaded"] = np.zeros(len(t), np.uint32)
+    if material:
+        out["material"] = np.zeros(len(t), np.uint32)
+    skipped = C.c_int64(0)
+
+    def ptr(a):
+        return _ptr(a) if a is not None and a.size else None
+    _lib.check_host(_lib.host_lib().mrth_scene_attributes(ptr(v), len(v), ptr(t), len(t), ptr(d),
+                                                          _ptr(out["normals"]) if normals else None,
+                                                          _ptr(out["shaded"]) if shaded else None,
+                                                          _ptr(out["material"]) if material else None,
+                                                          C.byref(skipped)))
+    out["skipped"] = int(skipped.value)
+    return out
 
 
 def woopify(v0, v1, v2) -> np.ndarray:

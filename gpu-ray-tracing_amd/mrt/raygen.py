@@ -26,6 +26,35 @@ def nscreen_to_world(cam: Camera, w: int, h: int) -> np.ndarray:
     return np.array(out, np.float32)
 
 
+def _geometry_on_device(dev, vertices, triangles, diffuse):
+    """vertices float32 [nv, 3], triangles int32 [nt, 3], diffuse float32 [nt, 4] or None as
+    contiguous tensors on dev; numpy input is uploaded (as in Tracer.refit)."""
+    def on_device(a, dtype, np_dtype, cols):
+        if isinstance(a, torch.Tensor):
+            return a.to(dev, dtype).contiguous().view(-1, cols)
+        a = np.ascontiguousarray(a, np_dtype).reshape(-1, cols)
+        return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+    v = on_device(vertices, torch.float32, np.float32, 3)
+    t = on_device(triangles, torch.int32, np.int32, 3)
+    d = None if diffuse is None else on_device(diffuse, torch.float32, np.float32, 4)
+    if d is not None and d.shape[0] != t.shape[0]:
+        raise _lib.MrtError("set_geometry: diffuse must hold 4 floats per triangle")
+    return v, t, d
+
+
+def scene_attributes(vertices: torch.Tensor, triangles: torch.Tensor, diffuse: torch.Tensor | None = None,
+                     normals: torch.Tensor | None = None, shaded: torch.Tensor | None = None,
+                     material: torch.Tensor | None = None, skipped: torch.Tensor | None = None, stream=None) -> None:
+    """mrt_scene_attributes over device tensors, written into the outputs given (float32 [nt, 3],
+    int32 [nt], int32 [nt]; at least one) on `stream`, with no host sync. skipped: an int64
+    device tensor the count of triangles with an out-of-range vertex index is ADDED to."""
+    def ptr(a):
+        return None if a is None else a.data_ptr()
+    _lib.check(_lib.trace_lib().mrt_scene_attributes(ptr(vertices), vertices.shape[0], ptr(triangles),
+                                                     triangles.shape[0], ptr(diffuse), ptr(normals), ptr(shaded),
+                                                     ptr(material), ptr(skipped), _stream_ptr(stream)))
+
+
 class DeviceRayGen:
     """RayGen on one device: primary rays, AO/diffuse rays, hit counts."""
 
@@ -39,6 +68,21 @@ class DeviceRayGen:
             _, _, normals = scene.arrays()
             self.normals = torch.from_numpy(np.ascontiguousarray(normals, np.float32)).to(self.device)
             self.num_tris = scene.num_triangles
+
+    def set_geometry(self, vertices, triangles, diffuse=None, stream=None) -> None:
+        """The triangle normals of moved (or new) vertices, computed on the device
+        (mrt_scene_attributes) on `stream` with no host sync: what ao / ao_blocks shoot their
+        hemispheres round from then on. vertices float32 [nv, 3], triangles int32 [nt, 3] as
+        device tensors; numpy arrays are uploaded. The normal tensor is rewritten in place; a
+        first call, or another triangle count, allocates it. diffuse is not needed here (the
+        signature is DeviceReconstructor.set_geometry's)."""
+        v, t, _ = _geometry_on_device(self.device, vertices, triangles, None)
+        nt = t.shape[0]
+        if self.normals is None or self.normals.shape[0] != nt:
+            self.normals = torch.empty((nt, 3), dtype=torch.float32, device=self.device)
+            self.num_tris = nt
+        scene_attributes(v, t, normals=self.normals, stream=stream)
+        self._geometry_inputs = (v, t)   # the launch may still read them
 
     def _table(self, w: int, h: int) -> torch.Tensor:
         if (w, h) not in self._tables:
@@ -136,12 +180,28 @@ class DeviceReconstructor:
     """Renderer's reconstruction step on one device (reference Renderer.cc:421-445 +
     reconstructKernel, RendererKernels.cu:60-108): traced batches -> ABGR pixels in HBM."""
 
-    def __init__(self, scene: Scene, device=None):
+    def __init__(self, scene: Scene | None, device=None):
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.lib = _lib.trace_lib()
-        mat, sh = scene.tri_colors()
-        self.material = torch.from_numpy(mat.view(np.int32)).to(self.device)
-        self.shaded = torch.from_numpy(sh.view(np.int32)).to(self.device)
+        self.material = self.shaded = None   # scene None: set_geometry makes them
+        if scene is not None:
+            mat, sh = scene.tri_colors()
+            self.material = torch.from_numpy(mat.view(np.int32)).to(self.device)
+            self.shaded = torch.from_numpy(sh.view(np.int32)).to(self.device)
+
+    def set_geometry(self, vertices, triangles, diffuse=None, stream=None) -> None:
+        """The shaded and material colours of moved (or new) vertices, computed on the device
+        (mrt_scene_attributes) on `stream` with no host sync. vertices float32 [nv, 3], triangles
+        int32 [nt, 3], diffuse float32 [nt, 4] (Scene.tri_diffuse(); None = the default material)
+        as device tensors; numpy arrays are uploaded. The colour tensors are rewritten in place;
+        a first call, or another triangle count, allocates them."""
+        v, t, d = _geometry_on_device(self.device, vertices, triangles, diffuse)
+        nt = t.shape[0]
+        if self.shaded is None or self.shaded.shape[0] != nt:
+            self.material = torch.empty(nt, dtype=torch.int32, device=self.device)
+            self.shaded = torch.empty(nt, dtype=torch.int32, device=self.device)
+        scene_attributes(v, t, d, shaded=self.shaded, material=self.material, stream=stream)
+        self._geometry_inputs = (v, t, d)   # the launch may still read them
 
     def reconstruct(self, ray_type: int, primary: RayBuffer, slot_to_id: torch.Tensor, num_pixels: int,
                     batch: RayBuffer | None = None, num_samples: int = 1, pixels: torch.Tensor | None = None,

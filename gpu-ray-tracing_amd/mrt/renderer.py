@@ -22,6 +22,7 @@ size and sample count is traced as several launches, like the reference.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -88,6 +89,10 @@ class Renderer:
         self._seeds: list[int] = []   # this frame's batch seeds, drawn from rand() in batch order
         self.sort_secondary, self.sort_drop_levels, self.sort_box = False, 0, 0
         self.batch_id_to_slot: torch.Tensor | None = None   # of a sorted batch; None = the identity layout
+        # set_vertices: the scene's triangles and diffuse colours on the device, the tree it rebuilt,
+        # and the SAH cost its rebuild decision compares against (of the GpuBvh _baseline_of)
+        self._triangles = self._diffuse = self._built = None
+        self._baseline_sah, self._baseline_of = None, None
 
     def set_params(self, ray_type: int = RAY_PRIMARY, num_samples: int = 1, ao_radius: float = 5.0,
                    sort_secondary: bool = False, sort_drop_levels: int = 0, sort_box: int = 0) -> None:
@@ -99,6 +104,51 @@ class Renderer:
             raise _lib.MrtError(f"sort_drop_levels {sort_drop_levels} outside 0..24 or sort_box {sort_box} outside 0..1")
         self.ray_type, self.num_samples, self.ao_radius = ray_type, int(num_samples), float(ao_radius)
         self.sort_secondary, self.sort_drop_levels, self.sort_box = bool(sort_secondary), int(sort_drop_levels), int(sort_box)
+
+    def set_vertices(self, vertices, stream=None, rebuild_above: float | None = None) -> dict:
+        """Moved vertices of the scene's triangles (float32 [nv, 3], a device tensor; a numpy array
+        is uploaded): the tracer's bound tree is refitted (Tracer.refit) and the normals and
+        colours the frame path reads are recomputed on the device (set_geometry of the ray
+        generator and the reconstructor), all on `stream`, nothing crossing to the host. Frames
+        begun afterwards on that stream see the moved scene.
+        rebuild_above=r: the refitted tree's SAH cost is then read (Tracer.tree_cost: one blocking
+        64-byte readback) and, where it exceeds r times the baseline, the tree is rebuilt from the
+        moved vertices (Tracer.build(..., on_device=True); the renderer keeps the GpuBvh alive) and
+        the new tree's cost becomes the baseline. The baseline is the cost of the tree as it stood
+        when this renderer first read one for the bound GpuBvh (so: pass rebuild_above from the
+        first call on, and it is the built or bound tree's). None (the default) never rebuilds,
+        reads no cost and adds no sync: no ratio has been shown to pay in general.
+        Returns {"rebuilt", "sah", "ratio"}: the refitted tree's cost and its ratio to the baseline
+        (what the decision was taken on), None where no cost was read."""
+        if self.tracer.bvh is None:
+            raise _lib.MrtError("Renderer.set_vertices: the tracer has no BVH")
+        dev = self.gen.device
+        if self._triangles is None:
+            _, tris, _ = self.scene.arrays()
+            self._triangles = torch.from_numpy(tris).to(dev)
+            self._diffuse = torch.from_numpy(self.scene.tri_diffuse()).to(dev)
+        if self._recon is None:
+            self._recon = DeviceReconstructor(self.scene)
+        if isinstance(vertices, torch.Tensor):
+            v = vertices.to(dev, torch.float32).contiguous().view(-1, 3)
+        else:
+            v = torch.from_numpy(np.array(vertices, np.float32).reshape(-1, 3)).to(dev)
+        if rebuild_above is not None and self._baseline_of is not self.tracer.bvh:
+            self._baseline_sah, self._baseline_of = self.tracer.tree_cost(stream)["sah"], self.tracer.bvh
+        self.tracer.refit(v, self._triangles, stream=stream)
+        self.gen.set_geometry(v, self._triangles, stream=stream)
+        self._recon.set_geometry(v, self._triangles, self._diffuse, stream=stream)
+        out = {"rebuilt": False, "sah": None, "ratio": None}
+        if rebuild_above is None:
+            return out
+        out["sah"] = self.tracer.tree_cost(stream)["sah"]
+        if out["sah"] is not None and self._baseline_sah:
+            out["ratio"] = out["sah"] / self._baseline_sah
+        if out["ratio"] is not None and out["ratio"] > rebuild_above:
+            self._built = self.tracer.build(v, self._triangles, stream=stream, on_device=True)
+            self._baseline_sah, self._baseline_of = self.tracer.tree_cost(stream)["sah"], self.tracer.bvh
+            out["rebuilt"] = True
+        return out
 
     def begin_frame(self, cam: Camera, w: int, h: int, subpixel=(0.5, 0.5)) -> None:
         self.cam, self.w, self.h = cam, w, h

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .host import Bvh
+from .host import Bvh, tree_cost_dict
 
 
 def _stream_ptr(stream) -> int | None:
@@ -135,6 +135,13 @@ class RayBuffer:
 
     def hit_t(self) -> np.ndarray:
         return self.results_numpy()[:, 1].view(np.float32)
+
+
+def tree_cost_from_tensor(t: torch.Tensor) -> dict:
+    """The dict Tracer.tree_cost(sync=True) gives, from the device tensor its sync=False form
+    returned (blocking copy; synchronise the stream it was enqueued on first)."""
+    raw = t.cpu().numpy().tobytes()
+    return tree_cost_dict(_lib.TreeCost.from_buffer_copy(raw))
 
 
 def refit_plan(nodes, wide: bool = True):
@@ -280,6 +287,23 @@ class Tracer:
         r = _lib.RefitInfo()
         _lib.check(self.lib.mrt_tracer_refit_info(self._h, C.byref(r)))
         return {k: getattr(r, k) for k, _ in r._fields_}
+
+    def tree_cost(self, stream=None, sync: bool = True):
+        """The bound tree's area sums, summed on the device (mrt_tracer_tree_cost): root_area,
+        inner_area, leaf_area, leaf_tri_area, records, leaves, triangles, skipped, and
+        sah = (Cn * inner_area + Ct * leaf_tri_area) / root_area (mrt.host.tree_cost_dict). Ordered
+        after a refit on `stream`. sync=True blocks for one 64-byte readback and returns the dict;
+        sync=False enqueues only and returns an 8-word float64 device tensor holding the
+        mrt_tree_cost bytes (mrt.tracer.tree_cost_from_tensor reads it after a sync)."""
+        if self.bvh is None:
+            raise _lib.MrtError("Tracer: No BVH!")
+        if sync:
+            c = _lib.TreeCost()
+            _lib.check(self.lib.mrt_tracer_tree_cost(self._h, C.byref(c), None, _stream_ptr(stream)))
+            return tree_cost_dict(c)
+        out = torch.empty(8, dtype=torch.float64, device=self.bvh.device)
+        _lib.check(self.lib.mrt_tracer_tree_cost(self._h, None, out.data_ptr(), _stream_ptr(stream)))
+        return out
 
     # -- re-optimise (treelet restructuring) ---------------------------------------
     def optimize(self, rounds: int = 1, stream=None) -> dict:

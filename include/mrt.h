@@ -342,7 +342,8 @@ int  mrt_tracer_last_kernel_key(const mrt_tracer* t);
  *   - Limits: a leaf box covers the whole triangle also where the SBVH builder had clipped
  *     the reference to a spatial split, so refitted boxes are correct but may be looser than
  *     built ones (traces get slower, never wrong); the tree is not re-optimised, so large
- *     deformations degrade it. When that shows, rebuild on the device (mrt_tracer_build_device:
+ *     deformations degrade it (mrt_tracer_tree_cost below reports the tree's SAH terms; DESIGN
+ *     §13 has how far they predict the trace). When that shows, rebuild on the device (mrt_tracer_build_device:
  *     1.65 ms for bunny) or, where the leaves must stay, restructure (mrt_tracer_optimize below:
  *     bunny displaced by 10 % of its size traced 0.93x after one round, 0.85x after three,
  *     0.77x after the rebuild); mrth_bvh_build + bind is the 20 s host route.
@@ -770,6 +771,75 @@ int  mrt_reconstruct(int32_t rayType, int32_t numRaysPerPrimary, int32_t firstPr
                      const int32_t* primarySlotToId, const void* primaryResults, const int32_t* batchIdToSlot,
                      const void* batchResults, const uint32_t* triMaterialColor, const uint32_t* triShadedColor,
                      uint32_t* pixels, void* stream);
+
+/* ---- a moving scene: normals, colours and the tree's cost on the device ---- */
+/* Scene::Scene's per-triangle tables (reference Scene.cc:37,66-80) from vertices in DEVICE
+ * memory: what mrt_raygen_ao / _ao_blocks read as triNormals and mrt_reconstruct as
+ * triShadedColor / triMaterialColor, kept current beside mrt_tracer_refit without the vertices
+ * crossing to the host. All pointers are device pointers on the calling thread's current device.
+ *   - triNormals: normalize(cross(v1 - v0, v2 - v0)), normalize being a * rcp(length(a)) with
+ *     rcp(0) = 0: a zero-area triangle gets the normal (0, 0, 0).
+ *   - triShadedColor: diffuse.xyz * (dot(n, normalize(1, 2, 3)) * 0.5 + 0.5), alpha 1, through the
+ *     host Vec4f::toABGR (Math.cc:45-52: in double, fixed point, its clamp sends a NaN channel to 0).
+ *     triMaterialColor: toABGR(diffuse). triDiffuse: 4 floats per triangle (mrth_scene_tri_diffuse),
+ *     NULL = the default material (0.75, 0.75, 0.75, 1; Mesh.hh:92).
+ *   - Parity: the arithmetic is csrc/scene_common.hpp's on both sides, and this part of the
+ *     library is built WITHOUT denormal flushing, without contraction or fast-math and with
+ *     correctly rounded division and square root (mrt_raygen_primary's part flushes; this one
+ *     does not). So every output equals mrth_scene_attributes' (mrt_host.h) bit for bit, denormal
+ *     coordinates, edges and normals included, and no input is excepted on account of the denormal
+ *     mode. The one difference is not arithmetic: the bits of a NaN that an operation makes (x86
+ *     0xFFC00000, gfx950 0x7FC00000), so a normal that is NaN on one side (a NaN or infinite
+ *     coordinate, an overflowing cross product) is NaN on the other with possibly other bits. The
+ *     colours are integers and equal in every case.
+ *   - A triangle with a vertex index outside [0, numVertices) never has that vertex read: it
+ *     gets the normal (0, 0, 0), is shaded accordingly, and *skipped (device int64, may be NULL)
+ *     is increased by one. The count is added to, never reset: clear it yourself.
+ *   - One launch, one lane per triangle, stream-ordered on `stream` (a hipStream_t, NULL = the null
+ *     stream): no host sync, no scratch, no readback. Outputs may be the tables a previous call
+ *     wrote; every entry is rewritten.
+ * numTriangles == 0 returns MRT_OK and launches nothing. MRT_ERR_INVALID_ARG for a negative count,
+ * all three outputs NULL, or NULL vertices / triangles with numTriangles > 0; MRT_ERR_TOO_LARGE
+ * above 67108863 triangles (mrt_tracer_refit's limit). In these cases nothing is written. */
+int  mrt_scene_attributes(const float* vertices, int64_t numVertices, const int32_t* triangles, int64_t numTriangles,
+                          const float* triDiffuse /* 4 floats per triangle; NULL = the default material */,
+                          float* triNormals /* 3 per triangle, may be NULL */,
+                          uint32_t* triShadedColor /* may be NULL */, uint32_t* triMaterialColor /* may be NULL */,
+                          int64_t* skipped /* device, may be NULL: added to, not reset */, void* stream);
+
+/* The area sums of the bound Compact2 tree: the terms of its SAH cost, for deciding whether a
+ * refitted tree has degraded enough to rebuild (mrt_tracer_refit's Limits). Areas are half
+ * surface areas dx*dy + dy*dz + dz*dx, the differences and products taken in double from the
+ * float32 planes of the bound Compact2 records (the array a refit writes, not the 4-wide copy).
+ * With Cn and Ct a platform's node and triangle costs,
+ * SAH = (Cn * inner_area + Ct * leaf_tri_area) / root_area. */
+typedef struct mrt_tree_cost {
+    double root_area;      /* area of the union of record 0's two boxes                    */
+    double inner_area;     /* sum over child slots that refer to a record, + root_area     */
+    double leaf_area;      /* sum over child slots that refer to a leaf                    */
+    double leaf_tri_area;  /* the same, each times its leaf's triangle count               */
+    int64_t records, leaves, triangles;
+    int64_t skipped;       /* slots whose area is not finite or whose box is inverted: in no sum */
+} mrt_tree_cost;
+
+/* Sums over every record of the bound array, two child slots each (a leaf's triangles: the walk
+ * from its first Woop slot in steps of three to its terminator, as in a refit; a leaf ref is
+ * followed only inside the Woop array). leaves and triangles count every leaf slot, skipped or
+ * not; a root union that is not finite or inverted gives root_area 0 and counts in skipped.
+ * One lane per slot, a reduction per wave, one partial per workgroup and a last step that adds
+ * the partials in index order: no floating-point atomics, so two calls on the same tree give the
+ * same bits. mrth_bvh_tree_cost (mrt_host.h) computes every slot's term with the same bits and
+ * adds them in record order: the counts are equal and each sum agrees within records * 2^-52
+ * relative (non-negative terms, two summation orders).
+ *   host != NULL: blocking, one readback of 64 bytes after the work enqueued on `stream`.
+ *   host == NULL, device != NULL (sizeof(mrt_tree_cost) bytes of device memory): stream-ordered,
+ *   no host sync. With both, the device copy is written and then read back.
+ * Scratch (48 bytes per 128 records) is taken and returned on the stream (hipMallocAsync /
+ * hipFreeAsync; a failed allocation is MRT_ERR_HIP). Ordered after a refit enqueued on `stream`
+ * before it. MRT_ERR_NOT_BOUND before a bind; MRT_ERR_INVALID_ARG with both outputs NULL. The
+ * records are not checked to form a tree: child refs to records are counted, never followed. */
+int  mrt_tracer_tree_cost(mrt_tracer* t, mrt_tree_cost* host /* may be NULL */,
+                          void* device /* sizeof(mrt_tree_cost) of device memory, may be NULL */, void* stream);
 
 /* ---- per-device convenience API (one implicit tracer per device) -------- */
 int  mrt_bind_bvh(const void* nodes, int64_t nodeBytes, const void* woop, int64_t woopBytes,

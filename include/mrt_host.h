@@ -77,6 +77,20 @@ int  mrth_scene_camera(const mrth_scene* s, mrth_camera* cam, float* aoRadius);
  * (diffuse 0.75 grey, Mesh.hh:92; synthetic scenes). Either output may be NULL; each
  * holds num_triangles uint32. */
 int  mrth_scene_tri_colors(const mrth_scene* s, uint32_t* material, uint32_t* shaded);
+/* Each triangle's material diffuse colour, 4 floats (rgb, alpha) per triangle: what
+ * mrth_scene_tri_colors shades, to hand to mrth_scene_attributes / mrt_scene_attributes as
+ * triDiffuse. The default material (0.75, 0.75, 0.75, 1) where the scene has no .mtl. */
+int  mrth_scene_tri_diffuse(const mrth_scene* s, float* out /* 4*nt */);
+/* The scene's per-triangle tables over plain arrays (no scene object): the CPU statement of
+ * mrt_scene_attributes (mrt.h), whose bits it gives (csrc/scene_common.hpp holds the arithmetic
+ * of both, and of mrth_scene_copy_arrays' normals and mrth_scene_tri_colors). Same arguments,
+ * outputs and rules: any output may be NULL but not all three; triDiffuse NULL = the default
+ * material; a triangle with a vertex index outside [0, numVertices) reads no vertex, gets the
+ * normal (0, 0, 0) and adds one to *skipped (may be NULL; added to, not reset). numTriangles == 0
+ * is MRTH_OK; MRTH_ERR_INVALID_ARG where mrt_scene_attributes refuses (too many triangles included). */
+int  mrth_scene_attributes(const float* vertices, int64_t numVertices, const int32_t* triangles, int64_t numTriangles,
+                           const float* triDiffuse, float* triNormals, uint32_t* triShadedColor,
+                           uint32_t* triMaterialColor, int64_t* skipped);
 
 /* ---- BVH (SBVH build -> Compact2 host buffers) ---------------------------- */
 void mrth_default_build_params(mrth_build_params* p);
@@ -150,6 +164,21 @@ typedef struct mrth_optimize_info {
     double  wall_ms;
 } mrth_optimize_info;
 int  mrth_bvh_optimize(mrth_bvh* b, int32_t rounds, mrth_optimize_info* info);
+/* The tree's area sums (the CPU statement of mrt_tracer_tree_cost, mrt.h; the layout is
+ * mrt_tree_cost's): half surface areas dx*dy + dy*dz + dz*dx in double from the float32 planes,
+ * every slot's term the device's bit for bit, added in record order, side 0 before side 1, the
+ * root's term last. leaves and triangles count every leaf slot; a slot whose area is not finite
+ * or whose box is inverted is counted in skipped and enters no sum, and so does the root union
+ * (root_area 0 then). Child refs are counted, never followed. */
+typedef struct mrth_tree_cost {
+    double root_area;      /* area of the union of record 0's two boxes                    */
+    double inner_area;     /* sum over child slots that refer to a record, + root_area     */
+    double leaf_area;      /* sum over child slots that refer to a leaf                    */
+    double leaf_tri_area;  /* the same, each times its leaf's triangle count               */
+    int64_t records, leaves, triangles;
+    int64_t skipped;
+} mrth_tree_cost;
+int  mrth_bvh_tree_cost(const mrth_bvh* b, mrth_tree_cost* out);
 /* Woop rows (Z,U,V; 12 floats) of one triangle, CudaBVH::woopifyTri. */
 void mrth_woopify(const float v0[3], const float v1[3], const float v2[3], float out[12]);
 
