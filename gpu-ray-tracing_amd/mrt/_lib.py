@@ -199,6 +199,9 @@ TRACE_SYMBOLS = [
     ("mrt_scene_attributes", i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
     ("mrt_tracer_tree_cost", i32, [vp, C.POINTER(TreeCost), vp, vp]),
     ("mrt_reconstruct", i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    ("mrt_raygen_shadow", i32, [vp, vp, i32, i32, C.POINTER(f32), f32, u32, vp, vp, vp, vp]),
+    ("mrt_raygen_shadow_blocks", i32, [vp, vp, i32, i32, C.POINTER(f32), f32, vp, i32, i32, vp, i32, i32, i64, vp, vp]),
+    ("mrt_reconstruct_lit", i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(f32), vp, vp]),
     ("mrt_selftest_exact_rcp", i32, [C.POINTER(C.c_uint64)]),
     ("bind_CudaBVHTexture", None, [vp, i64, vp, i64, vp, i64]),
     ("unbind_CudaBVHTexture", None, []),
@@ -250,6 +253,8 @@ HOST_SYMBOLS = [
     ("mrth_camera_decode_signature", i32, [C.c_char_p, C.POINTER(HostCamera), C.POINTER(f32), C.POINTER(i32)]),
     ("mrth_ao_rays", i32, [vp, vp, i64, vp, i32, f32, u32, vp]),
     ("mrth_count_hits", i64, [vp, i64]),
+    ("mrth_shadow_rays", i32, [vp, vp, i64, i32, C.POINTER(f32), f32, u32, vp]),
+    ("mrth_reconstruct_lit", i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(f32), vp]),
     ("mrth_ray_sort", i32, [vp, vp, i32, C.POINTER(RaySortParams), vp, vp, vp, vp, vp]),
     ("mrth_last_error", C.c_char_p, []),
 ]

@@ -352,6 +352,56 @@ def count_hits(results: np.ndarray) -> int:
     return int(_lib.host_lib().mrth_count_hits(_ptr(r), len(r)))
 
 
+def _light3(light):
+    a = np.asarray(light, np.float32).reshape(-1)
+    if a.shape != (3,):
+        raise _lib.MrtError("a light position is three floats")
+    return (C.c_float * 3)(*a.tolist())
+
+
+def shadow_rays(rays: np.ndarray, results: np.ndarray, num_samples: int, light, light_radius: float,
+                seed: int = AO_SEED, first: int = 0, count: int | None = None) -> np.ndarray:
+    """RayGen::shadow on the host (mrth_shadow_rays; the CPU statement of DeviceRayGen.shadow,
+    whose bits it gives): num_samples rays per input ray of [first, first + count) towards an
+    area light at `light` (a cube of half-side light_radius), tmax the distance to each sample.
+    The offset hash counts from the batch's first ray."""
+    p = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    r = np.ascontiguousarray(results).view(np.int32).reshape(-1, 4)
+    n = len(p) - first if count is None else count
+    if first < 0 or n < 0 or first + n > len(p) or len(r) != len(p):
+        raise _lib.MrtError(f"input range [{first}, {first + n}) outside the {len(p)}-ray batch")
+    out = np.empty((n * num_samples, 8), np.float32)
+    _lib.check_host(_lib.host_lib().mrth_shadow_rays(p.ctypes.data + 32 * first, r.ctypes.data + 16 * first, n,
+                                                     num_samples, _light3(light), float(light_radius),
+                                                     seed & 0xFFFFFFFF, _ptr(out) if out.size else None))
+    return out
+
+
+def reconstruct_lit(num_samples: int, slot_to_id, primary_rays, primary_results, batch_results, normals, material,
+                    light, num_pixels: int, batch_id_to_slot=None, first_primary: int = 0,
+                    num_primary: int | None = None, pixels: np.ndarray | None = None) -> np.ndarray:
+    """mrth_reconstruct_lit (the CPU statement of DeviceReconstructor.reconstruct_lit, whose bits
+    it gives): num_pixels uint32 ABGR pixels, untouched ones 0 (or `pixels`' own)."""
+    s2i = np.ascontiguousarray(slot_to_id, np.int32)
+    pr = np.ascontiguousarray(primary_rays, np.float32).reshape(-1, 8)
+    pres = np.ascontiguousarray(primary_results).view(np.int32).reshape(-1, 4)
+    bres = np.ascontiguousarray(batch_results).view(np.int32).reshape(-1, 4)
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    mat = np.ascontiguousarray(material).view(np.uint32).reshape(-1)
+    b2s = None if batch_id_to_slot is None else np.ascontiguousarray(batch_id_to_slot, np.int32)
+    if num_primary is None:
+        num_primary = len(bres) // num_samples
+    if (first_primary < 0 or first_primary + num_primary > len(pr) or len(pres) != len(pr) or len(s2i) != len(pr)
+            or len(bres) < num_primary * num_samples or (b2s is not None and len(b2s) < num_primary * num_samples)):
+        raise _lib.MrtError("reconstruct_lit: the batch does not fit the primary batch")
+    if pixels is None:
+        pixels = np.zeros(num_pixels, np.uint32)
+    _lib.check_host(_lib.host_lib().mrth_reconstruct_lit(num_samples, first_primary, num_primary, _ptr(s2i), _ptr(pr),
+                                                         _ptr(pres), None if b2s is None else _ptr(b2s), _ptr(bres),
+                                                         _ptr(nrm), _ptr(mat), _light3(light), _ptr(pixels)))
+    return pixels
+
+
 def ray_sort(rays, slot_to_id=None, drop_levels: int = 0, box: int = 0) -> dict:
     """RayBuffer::mortonSort on the host (mrth_ray_sort; the CPU statement of
     RayBuffer.morton_sort, whose bits it reproduces): the batch in the order of the reference's

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .host import AO_SEED, Camera, Scene, pixel_table
+from .host import AO_SEED, Camera, Scene, _light3, pixel_table
 from .tracer import RayBuffer, _stream_ptr
 
 
@@ -144,6 +144,38 @@ class DeviceRayGen:
                                                  _stream_ptr(stream)))
         return RayBuffer(out, need_closest_hit=closest_hit, device=self.device, secondary=True)
 
+    def shadow(self, rays: RayBuffer, num_samples: int, light, light_radius: float, seed: int = AO_SEED,
+               stream=None, first: int = 0, count: int | None = None) -> RayBuffer:
+        """RayGen::shadow over a traced batch (mrt_raygen_shadow): num_samples any-hit rays per
+        input ray from the traced point towards samples of an area light at `light` (a cube of
+        half-side light_radius), each with tmax = the distance to its sample (-1 where the input
+        ray missed). first/count select the input rays [first, first + count), one batch of
+        RayGen::batching; the offset hash and the output slots count from the batch's first ray.
+        Bit-identical to mrt.host.shadow_rays."""
+        n = rays.size - first if count is None else count
+        if first < 0 or n < 0 or first + n > rays.size:
+            raise _lib.MrtError(f"input range [{first}, {first + n}) outside the {rays.size}-ray batch")
+        out = torch.empty((n * num_samples, 8), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mrt_raygen_shadow(rays.rays.data_ptr() + 32 * first, rays.results.data_ptr() + 16 * first,
+                                              n, num_samples, _light3(light), float(light_radius), seed & 0xFFFFFFFF,
+                                              out.data_ptr(), None, None, _stream_ptr(stream)))
+        return RayBuffer(out, need_closest_hit=False, device=self.device, secondary=True)
+
+    def shadow_blocks(self, rays: RayBuffer, num_samples: int, light, light_radius: float, seeds, batch_inputs: int,
+                      blocks: torch.Tensor, block_rays: int, num_rays: int, stream=None) -> RayBuffer:
+        """The frame's shadow rays for a list of blocks of its ray order (mrt_raygen_shadow_blocks):
+        ao_blocks' contract with shadow's rays, bit-identical to the batches' at those positions."""
+        if blocks.dtype != torch.int32 or blocks.dim() != 1 or blocks.device != torch.device(self.device):
+            raise _lib.MrtError("shadow_blocks: blocks must be a 1-D int32 tensor on the generator's device")
+        sd = (C.c_uint32 * max(1, len(seeds)))(*[s & 0xFFFFFFFF for s in seeds])
+        out = torch.empty((num_rays, 8), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mrt_raygen_shadow_blocks(rays.rays.data_ptr(), rays.results.data_ptr(), rays.size,
+                                                     num_samples, _light3(light), float(light_radius),
+                                                     C.cast(sd, C.c_void_p), len(seeds), batch_inputs,
+                                                     blocks.data_ptr(), blocks.numel(), block_rays, num_rays,
+                                                     out.data_ptr(), _stream_ptr(stream)))
+        return RayBuffer(out, need_closest_hit=False, device=self.device, secondary=True)
+
     def shard_blocks(self, primary: RayBuffer, num_samples: int, block_rays: int, world: int, rank: int,
                      order: int = 1, stream=None) -> tuple[torch.Tensor, int]:
         """mrt_shard_blocks: rank's blocks (block i to rank i % world) of the frame's AO/diffuse
@@ -173,7 +205,7 @@ class DeviceRayGen:
         return int(self.count_hits_async(rays, stream).item())
 
 
-RAY_PRIMARY, RAY_AO, RAY_DIFFUSE = 0, 1, 2
+RAY_PRIMARY, RAY_AO, RAY_DIFFUSE, RAY_SHADOW = 0, 1, 2, 3
 
 
 class DeviceReconstructor:
@@ -229,4 +261,32 @@ class DeviceReconstructor:
                                             primary.results.data_ptr(), b2s, batch.results.data_ptr(),
                                             self.material.data_ptr(), self.shaded.data_ptr(), pixels.data_ptr(),
                                             _stream_ptr(stream)))
+        return pixels
+
+    def reconstruct_lit(self, primary: RayBuffer, slot_to_id: torch.Tensor, num_pixels: int, batch: RayBuffer,
+                        num_samples: int, normals: torch.Tensor, light, pixels: torch.Tensor | None = None,
+                        batch_id_to_slot: torch.Tensor | None = None, stream=None, first_primary: int = 0) -> torch.Tensor:
+        """A traced shadow batch into pixels (mrt_reconstruct_lit): per primary of the batch, the
+        share of its num_samples shadow rays that reached the light, times the cosine between the
+        hit triangle's normal (normals: float32 [nt, 3] on the device, DeviceRayGen.normals) and
+        the direction to `light`, times the triangle's material colour; the background where the
+        primary missed. The batch covers the primaries [first_primary, first_primary + batch.size
+        / num_samples), as in reconstruct. Bit-identical to mrt.host.reconstruct_lit."""
+        if batch.size % num_samples:
+            raise _lib.MrtError(f"batch holds {batch.size} rays, not a multiple of {num_samples}")
+        n_primary = batch.size // num_samples
+        if first_primary < 0 or first_primary + n_primary > primary.size:
+            raise _lib.MrtError(f"batch covers primaries [{first_primary}, {first_primary + n_primary}) "
+                                f"outside the {primary.size}-ray primary batch")
+        if slot_to_id.numel() != primary.size:
+            raise _lib.MrtError("slot_to_id must hold one pixel id per primary ray")
+        if normals is None or normals.dtype != torch.float32 or normals.numel() != 3 * self.material.numel():
+            raise _lib.MrtError("reconstruct_lit needs one float32 normal per triangle of the colour table")
+        if pixels is None:
+            pixels = torch.zeros(num_pixels, dtype=torch.int32, device=self.device)
+        b2s = None if batch_id_to_slot is None else batch_id_to_slot.data_ptr()
+        _lib.check(self.lib.mrt_reconstruct_lit(num_samples, first_primary, n_primary, slot_to_id.data_ptr(),
+                                                primary.rays.data_ptr(), primary.results.data_ptr(), b2s,
+                                                batch.results.data_ptr(), normals.data_ptr(), self.material.data_ptr(),
+                                                _light3(light), pixels.data_ptr(), _stream_ptr(stream)))
         return pixels

@@ -14,6 +14,10 @@ and RayGen's batching (src/rt/ray/RayGen.cc:77-142) over the C-ABI.
   traceBatch      Renderer.cc:295-300   CudaTracer::traceBatch of the current batch -> ms
   updateResult    Renderer.cc:421-445   reconstructKernel of the batch into the frame's pixels
 
+A fourth ray type, RAY_SHADOW, runs the generator the reference wrote and never launched
+(RayGen::shadow, RayGen.cc:147-183): batches of any-hit rays from the primary hits towards an area
+light, batched and seeded like AO, reconstructed by DeviceReconstructor.reconstruct_lit.
+
 The reference draws every AO/diffuse batch seed from the C library's rand()
 (RayGen.cc:106; App never seeds it, so the sequence starts at glibc's
 1804289383); GlibcRand restates glibc's TYPE_3 generator so batch k of a frame
@@ -27,7 +31,7 @@ import torch
 
 from . import _lib
 from .host import Camera, Scene
-from .raygen import RAY_AO, RAY_DIFFUSE, RAY_PRIMARY, DeviceRayGen, DeviceReconstructor
+from .raygen import RAY_AO, RAY_DIFFUSE, RAY_PRIMARY, RAY_SHADOW, DeviceRayGen, DeviceReconstructor
 from .tracer import RayBuffer, Tracer
 
 MAX_BATCH_RAYS = 1 << 21   # Renderer.cc:46 m_raygen(1 << 21)
@@ -80,6 +84,7 @@ class Renderer:
         self.gen = DeviceRayGen(scene)
         self._recon = None
         self.ray_type, self.num_samples, self.ao_radius = RAY_PRIMARY, 1, 5.0
+        self.light_pos, self.light_radius = (0.0, 0.0, 0.0), 0.0
         self.primary: RayBuffer | None = None
         self.slot_to_id: torch.Tensor | None = None
         self.batch: RayBuffer | None = None
@@ -95,14 +100,20 @@ class Renderer:
         self._baseline_sah, self._baseline_of = None, None
 
     def set_params(self, ray_type: int = RAY_PRIMARY, num_samples: int = 1, ao_radius: float = 5.0,
-                   sort_secondary: bool = False, sort_drop_levels: int = 0, sort_box: int = 0) -> None:
-        """sort_secondary: Morton-sort every AO / diffuse batch before it is traced (the reference's
-        sortSecondary); sort_drop_levels / sort_box: RayBuffer.morton_sort's drop_levels and box."""
-        if ray_type not in (RAY_PRIMARY, RAY_AO, RAY_DIFFUSE):
+                   sort_secondary: bool = False, sort_drop_levels: int = 0, sort_box: int = 0,
+                   light_pos=(0.0, 0.0, 0.0), light_radius: float = 0.0) -> None:
+        """sort_secondary: Morton-sort every AO / diffuse / shadow batch before it is traced (the
+        reference's sortSecondary); sort_drop_levels / sort_box: RayBuffer.morton_sort's drop_levels
+        and box. light_pos / light_radius: the area light of a RAY_SHADOW frame (a cube of half-side
+        light_radius round light_pos, as the reference samples it); the other types ignore them."""
+        if ray_type not in (RAY_PRIMARY, RAY_AO, RAY_DIFFUSE, RAY_SHADOW):
             raise _lib.MrtError(f"unknown ray type {ray_type}")
+        if len(tuple(light_pos)) != 3:
+            raise _lib.MrtError("light_pos is three floats")
         if not 0 <= int(sort_drop_levels) <= 24 or int(sort_box) not in (0, 1):
             raise _lib.MrtError(f"sort_drop_levels {sort_drop_levels} outside 0..24 or sort_box {sort_box} outside 0..1")
         self.ray_type, self.num_samples, self.ao_radius = ray_type, int(num_samples), float(ao_radius)
+        self.light_pos, self.light_radius = tuple(float(x) for x in light_pos), float(light_radius)
         self.sort_secondary, self.sort_drop_levels, self.sort_box = bool(sort_secondary), int(sort_drop_levels), int(sort_box)
 
     def set_vertices(self, vertices, stream=None, rebuild_above: float | None = None) -> dict:
@@ -180,9 +191,13 @@ class Renderer:
             return False
         lo, hi = rng
         self._next_input = hi
-        self.batch = self.gen.ao(self.primary, self.num_samples, self._max_dist(),
-                                 seed=self.batch_seeds(lo // self._batch_inputs() + 1)[-1],
-                                 closest_hit=self.ray_type == RAY_DIFFUSE, first=lo, count=hi - lo)
+        seed = self.batch_seeds(lo // self._batch_inputs() + 1)[-1]
+        if self.ray_type == RAY_SHADOW:
+            self.batch = self.gen.shadow(self.primary, self.num_samples, self.light_pos, self.light_radius,
+                                         seed=seed, first=lo, count=hi - lo)
+        else:
+            self.batch = self.gen.ao(self.primary, self.num_samples, self._max_dist(), seed=seed,
+                                     closest_hit=self.ray_type == RAY_DIFFUSE, first=lo, count=hi - lo)
         if self.sort_secondary:    # Renderer.cc:287-288
             self.batch, self.batch_id_to_slot, _ = self.batch.morton_sort(drop_levels=self.sort_drop_levels,
                                                                           box=self.sort_box)
@@ -216,7 +231,11 @@ class Renderer:
         A frame of any number of batches (any max_batch next_batch accepts): above 256 the
         generator reads the batch seeds from device scratch instead of its arguments."""
         if self.ray_type == RAY_PRIMARY or self.primary is None:
-            raise _lib.MrtError("secondary_blocks needs an AO or diffuse frame (set_params, begin_frame)")
+            raise _lib.MrtError("secondary_blocks needs an AO, diffuse or shadow frame (set_params, begin_frame)")
+        if self.ray_type == RAY_SHADOW:
+            return self.gen.shadow_blocks(self.primary, self.num_samples, self.light_pos, self.light_radius,
+                                          self.batch_seeds(), self._batch_inputs(), blocks, block_rays, num_rays,
+                                          stream=stream)
         return self.gen.ao_blocks(self.primary, self.num_samples, self._max_dist(), self.batch_seeds(),
                                   self._batch_inputs(), blocks, block_rays, num_rays,
                                   closest_hit=self.ray_type == RAY_DIFFUSE, stream=stream)
@@ -230,7 +249,7 @@ class Renderer:
         block_rays >= 1 and any number of batches: the limit is the frame's, 2^31 - 1 rays (a
         shard of more than 16 384 blocks is ordered in tiles, with stream-ordered scratch)."""
         if self.ray_type == RAY_PRIMARY or self.primary is None:
-            raise _lib.MrtError("shard needs an AO or diffuse frame (set_params, begin_frame)")
+            raise _lib.MrtError("shard needs an AO, diffuse or shadow frame (set_params, begin_frame)")
         blocks, n = self.gen.shard_blocks(self.primary, self.num_samples, block_rays, world, rank, order, stream)
         return self.secondary_blocks(blocks, n, block_rays, stream)
 
@@ -244,6 +263,11 @@ class Renderer:
         if self._recon is None:
             self._recon = DeviceReconstructor(self.scene)
         n = 1 if self.ray_type == RAY_PRIMARY else self.num_samples
+        if self.ray_type == RAY_SHADOW:   # the generator's normals: the ones set_vertices keeps current
+            return self._recon.reconstruct_lit(self.primary, self.slot_to_id, self.w * self.h, self.batch, n,
+                                               self.gen.normals, self.light_pos, pixels=pixels,
+                                               first_primary=self.batch_start // n,
+                                               batch_id_to_slot=self.batch_id_to_slot)
         return self._recon.reconstruct(self.ray_type, self.primary, self.slot_to_id, self.w * self.h, self.batch,
                                        num_samples=n, pixels=pixels, first_primary=self.batch_start // n,
                                        batch_id_to_slot=self.batch_id_to_slot)

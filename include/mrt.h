@@ -751,8 +751,9 @@ int  mrt_ray_sort(const void* inRays, const int32_t* inSlotToId /* NULL = identi
  * results with id >= 0. */
 int  mrt_count_hits(const void* results, int32_t numRays, int32_t* hitCount, void* stream);
 
-/* ray types of a batch (reference RayType_Primary / _AO / _Diffuse, App.cc) */
-enum { MRT_RAY_PRIMARY = 0, MRT_RAY_AO = 1, MRT_RAY_DIFFUSE = 2 };
+/* ray types of a batch (reference RayType_Primary / _AO / _Diffuse, App.cc); MRT_RAY_SHADOW is
+ * the frame type of mrt_raygen_shadow / mrt_reconstruct_lit below (mrt_reconstruct refuses it) */
+enum { MRT_RAY_PRIMARY = 0, MRT_RAY_AO = 1, MRT_RAY_DIFFUSE = 2, MRT_RAY_SHADOW = 3 };
 
 /* reconstructKernel (RendererKernels.cu:60-108; ReconstructInput RendererKernels.hh:46-61,
  * filled by Renderer.cc:421-445): one ABGR pixel per primary ray of the batch, at
@@ -771,6 +772,59 @@ int  mrt_reconstruct(int32_t rayType, int32_t numRaysPerPrimary, int32_t firstPr
                      const int32_t* primarySlotToId, const void* primaryResults, const int32_t* batchIdToSlot,
                      const void* batchResults, const uint32_t* triMaterialColor, const uint32_t* triShadedColor,
                      uint32_t* pixels, void* stream);
+
+/* ---- an area light: shadow rays and direct lighting ----
+ * RayGen::shadow + rayGenShadowKernel (RayGen.cc:147-183, which the reference leaves commented
+ * out, and RayGenKernels.cu:231-293): numSamples rays per input ray from the traced point towards
+ * samples of a light, for an any-hit trace; each ray's tmax is the distance to its own sample.
+ *   - origin = o + d * max(t - 1e-4, 0) (a NaN t backs off by 0), as in mrt_raygen_ao.
+ *   - Sample i of n: (sobol2D(i), (i + 0.5) / n) shifted by a per-ray offset (jenkinsMix twice over
+ *     (seed + ray index, 0x9e3779b9, 0x9e3779b9), each word times 2^-32 after a round-to-nearest
+ *     conversion, so an offset of exactly 1 occurs), wrapped once (`if (p >= 1) p -= 1`) and mapped
+ *     to [-1, 1)^3: pos. target = light + lightRadius * pos: the samples fill a CUBE of half-side
+ *     lightRadius, as in the reference. The ray index is the input ray's index within the call.
+ *   - direction = (target - origin) * rcp(length), rcp(0) = 0: a sample on the origin gives a zero
+ *     direction and tmax 0; a length that overflows to infinity gives a zero direction and tmax inf.
+ *     tmin = 0; tmax = -1 where the input id is -1. No table is read: every other id gives a live ray.
+ *   - Parity: the arithmetic is csrc/light_common.hpp's on both sides and this part of the library
+ *     is built like mrt_scene_attributes' (no denormal flushing, no contraction, correctly rounded
+ *     division and square root), so the rays equal mrth_shadow_rays' (mrt_host.h) bit for bit; only
+ *     the bits of a NaN that an operation makes differ.
+ * inRays / outRays must be 16-byte aligned (rays move as two 16-byte halves). outIdToSlot /
+ * outSlotToId (may be NULL) get the identity. numInputRays == 0 returns MRT_OK and launches nothing;
+ * a negative count, numSamples < 1 or a NULL required pointer is MRT_ERR_INVALID_ARG, more than
+ * INT32_MAX output rays MRT_ERR_TOO_LARGE, and nothing is written. Stream-ordered, no host sync. */
+int  mrt_raygen_shadow(const void* inRays, const void* inResults, int32_t numInputRays, int32_t numSamples,
+                       const float light[3], float lightRadius, uint32_t seed, void* outRays, int32_t* outIdToSlot,
+                       int32_t* outSlotToId, void* stream);
+
+/* A whole frame's shadow rays for a list of blocks of the frame's ray order: mrt_raygen_ao_blocks'
+ * contract exactly (batches, seeds, blocks, the partial last block, numOutRays, the seed table
+ * above 256 batches, the checks and their order), with mrt_raygen_shadow's rays: output ray j is
+ * bit-identical to the ray the batches hold at blocks[j / blockRays] * blockRays + j % blockRays. */
+int  mrt_raygen_shadow_blocks(const void* inRays, const void* inResults, int32_t numInputRays, int32_t numSamples,
+                              const float light[3], float lightRadius, const uint32_t* batchSeeds,
+                              int32_t numBatches, int32_t batchInputRays, const int32_t* blocks, int32_t numBlocks,
+                              int32_t blockRays, int64_t numOutRays, void* outRays, void* stream);
+
+/* A shadow batch's pixels: one ABGR pixel per primary ray of the batch, at
+ * pixels[primarySlotToId[firstPrimary + i]], i < numPrimary. A primary miss (id -1) gets the
+ * background (0.2, 0.4, 0.8). Otherwise, with u of the primary's numRaysPerPrimary batch results
+ * (batchIdToSlot[i * numRaysPerPrimary + k]; NULL = identity, mrt_raygen_shadow's layout) having
+ * id -1 — shadow rays that reached their light samples — v = u * (1 / numRaysPerPrimary),
+ * k = max(dot(nf, l), 0) with l the unit vector from the backed-off hit point to the light's
+ * centre and nf the hit triangle's normal turned against the primary ray (a NaN gives 0), and the
+ * pixel is (material.xyz * (k * v), 1) through the reference's device fromABGR / truncating toABGR
+ * (RendererKernels.cu:38-56). primaryRays (16-byte aligned) are the rays primaryResults belong to.
+ * The caller's contract, as in mrt_reconstruct: every primary id lies in [-1, entries of triNormals
+ * and triMaterialColor). The arithmetic is csrc/light_common.hpp's: mrth_reconstruct_lit (mrt_host.h)
+ * gives the same pixels bit for bit. numPrimary == 0 returns MRT_OK and launches nothing; a bad
+ * shape or a NULL pointer (all but batchIdToSlot are required) is MRT_ERR_INVALID_ARG and nothing
+ * is written. Stream-ordered, no host sync. */
+int  mrt_reconstruct_lit(int32_t numRaysPerPrimary, int32_t firstPrimary, int32_t numPrimary,
+                         const int32_t* primarySlotToId, const void* primaryRays, const void* primaryResults,
+                         const int32_t* batchIdToSlot, const void* batchResults, const float* triNormals,
+                         const uint32_t* triMaterialColor, const float light[3], uint32_t* pixels, void* stream);
 
 /* ---- a moving scene: normals, colours and the tree's cost on the device ---- */
 /* Scene::Scene's per-triangle tables (reference Scene.cc:37,66-80) from vertices in DEVICE

@@ -202,6 +202,19 @@ int  mrth_ao_rays(const void* primaryRays, const void* primaryResults, int64_t n
                   const mrth_scene* s, int32_t numSamples, float maxDist, uint32_t seed,
                   void* outRays /* numPrimary * numSamples Ray */);
 int64_t mrth_count_hits(const void* results, int64_t n);
+/* The CPU statements of mrt_raygen_shadow and mrt_reconstruct_lit (mrt.h, which states the rays
+ * and the pixels), with the same arguments over HOST memory and no stream, built from the same
+ * header (csrc/light_common.hpp): the same bits. Ray index = the input ray's index within the call.
+ * A count of 0 returns MRTH_OK and writes nothing; a negative count, numSamples < 1, more than
+ * 2^31 - 1 output rays or a NULL required pointer is MRTH_ERR_INVALID_ARG. */
+int  mrth_shadow_rays(const void* inRays, const void* inResults, int64_t numInputRays, int32_t numSamples,
+                      const float light[3], float lightRadius, uint32_t seed,
+                      void* outRays /* numInputRays * numSamples Ray */);
+int  mrth_reconstruct_lit(int32_t numRaysPerPrimary, int32_t firstPrimary, int32_t numPrimary,
+                          const int32_t* primarySlotToId, const void* primaryRays, const void* primaryResults,
+                          const int32_t* batchIdToSlot /* NULL = identity */, const void* batchResults,
+                          const float* triNormals, const uint32_t* triMaterialColor, const float light[3],
+                          uint32_t* pixels);
 
 /* RayBuffer::mortonSort (RayBuffer.cc:256-324): the CPU statement of mrt_ray_sort (mrt.h, which
  * states the key and the order), with the same arguments over HOST memory and no stream. outBox

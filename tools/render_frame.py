@@ -10,6 +10,12 @@ trace time, App.cc:204).
       --width 640 --height 480 --out gpurun_out/sponza-diffuse.ppm
   python tools/render_frame.py --obj conference.obj --ao-radius 5 --ray-type ao \
       --camera "6omr/04j3200bR6Z/0/3ZEAz/x4smy19///c/05frY109Qx7w////m100"
+  python tools/render_frame.py --scene bunny --ray-type shadow --samples 16 --light 0.2 1.5 2.0 \
+      --light-radius 0.2
+
+--ray-type shadow lights the frame from an area light (--light x y z, --light-radius r: a cube of
+half-side r, as the reference's shadow generator samples it); without --light the light sits at
+(0.5, 0.9, 0.9) of the scene's box with a radius of a fiftieth of its diagonal.
 """
 from __future__ import annotations
 
@@ -24,11 +30,11 @@ sys.path.insert(0, os.path.join(REPO, "gpu-ray-tracing_amd"))
 import torch  # noqa: E402
 
 import mrt  # noqa: E402
-from mrt.raygen import RAY_AO, RAY_DIFFUSE, RAY_PRIMARY  # noqa: E402
+from mrt.raygen import RAY_AO, RAY_DIFFUSE, RAY_PRIMARY, RAY_SHADOW  # noqa: E402
 from mrt.renderer import Renderer  # noqa: E402
 from mrt.tracer import GpuBvh, Tracer  # noqa: E402
 
-TYPES = {"primary": RAY_PRIMARY, "ao": RAY_AO, "diffuse": RAY_DIFFUSE}
+TYPES = {"primary": RAY_PRIMARY, "ao": RAY_AO, "diffuse": RAY_DIFFUSE, "shadow": RAY_SHADOW}
 
 
 def main() -> int:
@@ -39,6 +45,8 @@ def main() -> int:
     ap.add_argument("--ao-radius", type=float, default=None, help="the App's --ao-radius (default: the scene's)")
     ap.add_argument("--ray-type", choices=sorted(TYPES), default="primary")
     ap.add_argument("--samples", type=int, default=8)
+    ap.add_argument("--light", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="shadow: the light's centre")
+    ap.add_argument("--light-radius", type=float, default=None, help="shadow: half the side of the light's cube")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--out", default="gpurun_out/frame.ppm")
@@ -55,7 +63,14 @@ def main() -> int:
     tracer.set_bvh(GpuBvh(mrt.Bvh.build(scene).buffers()))
     w, h, rt = a.width, a.height, TYPES[a.ray_type]
     r = Renderer(tracer, scene)
-    r.set_params(rt, 1 if rt == RAY_PRIMARY else a.samples, ao_radius)
+    light, light_radius = a.light, a.light_radius
+    if rt == RAY_SHADOW and (light is None or light_radius is None):
+        v, _, _ = scene.arrays()
+        lo, hi = v.min(axis=0).astype(float), v.max(axis=0).astype(float)
+        light = light if light is not None else [float(x) for x in lo + (hi - lo) * (0.5, 0.9, 0.9)]
+        light_radius = light_radius if light_radius is not None else float(0.02 * ((hi - lo) ** 2).sum() ** 0.5)
+    r.set_params(rt, 1 if rt == RAY_PRIMARY else a.samples, ao_radius, light_pos=light or (0.0, 0.0, 0.0),
+                 light_radius=light_radius or 0.0)
     r.begin_frame(cam, w, h)
     counted = r.total_num_rays()
     pixels = torch.zeros(w * h, dtype=torch.int32, device="cuda")
@@ -68,7 +83,7 @@ def main() -> int:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     mrt.write_ppm(a.out, pixels.cpu().numpy(), w, h)
     print(json.dumps({"scene": a.obj or a.scene, "camera": a.camera, "ray_type": a.ray_type, "width": w, "height": h,
-                      "samples": r.num_samples, "batches": batches, "trace_ms": round(ms, 4), "rays_counted": counted,
+                      "samples": r.num_samples, "light": light, "light_radius": light_radius, "batches": batches, "trace_ms": round(ms, 4), "rays_counted": counted,
                       "mrays_per_s": round(counted / ms / 1e3, 2) if ms > 0 else None, "image": a.out}))
     return 0
 
