@@ -101,6 +101,20 @@ class RaySortParams(C.Structure):
     _fields_ = [("drop_levels", i32), ("box", i32)]
 
 
+class PathExtendParams(C.Structure):
+    """mrt_path_extend_params / mrth_path_extend_params (one layout)."""
+    _fields_ = [("vertex", i32), ("depth", i32), ("numSamples", i32), ("seed", u32), ("lightPos", f32 * 3),
+                ("lightRadius", f32), ("lightColor", f32 * 3), ("sky", f32 * 3), ("maxDist", f32), ("compact", i32),
+                ("triNormals", vp), ("triMaterialColor", vp), ("numTris", i64), ("numSlots", i32), ("numPaths", i32),
+                ("inRays", vp), ("inResults", vp), ("inState", vp), ("outShadowRays", vp), ("outPending", vp),
+                ("outRays", vp), ("outState", vp), ("radiance", vp), ("liveCount", vp)]
+
+
+MRT_PATH_MAX_PATHS = 1 << 22    # csrc/path_limits.hpp
+MRT_PATH_MAX_DEPTH = 64
+MRT_PATH_SCAN_ROUND_SLOTS = 1024 * 256   # slots whose workgroup counts fill one round of the scan
+
+
 class MortonKey(C.Structure):
     """RayBufferKernels.hh:46-50 (mrt.h mrt_morton_key)."""
     _fields_ = [("oldSlot", i32), ("hash", u32 * 6)]
@@ -202,6 +216,9 @@ TRACE_SYMBOLS = [
     ("mrt_raygen_shadow", i32, [vp, vp, i32, i32, C.POINTER(f32), f32, u32, vp, vp, vp, vp]),
     ("mrt_raygen_shadow_blocks", i32, [vp, vp, i32, i32, C.POINTER(f32), f32, vp, i32, i32, vp, i32, i32, i64, vp, vp]),
     ("mrt_reconstruct_lit", i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(f32), vp, vp]),
+    ("mrt_path_extend", i32, [C.POINTER(PathExtendParams), vp]),
+    ("mrt_path_accumulate", i32, [i32, i32, vp, vp, vp, vp, vp]),
+    ("mrt_path_resolve", i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     ("mrt_selftest_exact_rcp", i32, [C.POINTER(C.c_uint64)]),
     ("bind_CudaBVHTexture", None, [vp, i64, vp, i64, vp, i64]),
     ("unbind_CudaBVHTexture", None, []),
@@ -255,6 +272,9 @@ HOST_SYMBOLS = [
     ("mrth_count_hits", i64, [vp, i64]),
     ("mrth_shadow_rays", i32, [vp, vp, i64, i32, C.POINTER(f32), f32, u32, vp]),
     ("mrth_reconstruct_lit", i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(f32), vp]),
+    ("mrth_path_extend", i32, [C.POINTER(PathExtendParams)]),
+    ("mrth_path_accumulate", i32, [i32, i32, vp, vp, vp, vp]),
+    ("mrth_path_resolve", i32, [i32, i32, i32, vp, vp, vp, vp, vp]),
     ("mrth_ray_sort", i32, [vp, vp, i32, C.POINTER(RaySortParams), vp, vp, vp, vp, vp]),
     ("mrth_last_error", C.c_char_p, []),
 ]

@@ -402,6 +402,96 @@ def reconstruct_lit(num_samples: int, slot_to_id, primary_rays, primary_results,
     return pixels
 
 
+def path_params(vertex: int, depth: int, num_samples: int, seed: int, light_pos, light_radius: float,
+                light_color=(1.0, 1.0, 1.0), sky=(0.2, 0.4, 0.8), max_dist: float = 1.0e30,
+                compact: bool = True) -> "_lib.PathExtendParams":
+    """The scalar part of mrt_path_extend_params / mrth_path_extend_params; the caller sets the
+    tables, counts and buffers."""
+    p = _lib.PathExtendParams()
+    p.vertex, p.depth, p.numSamples, p.seed = int(vertex), int(depth), int(num_samples), seed & 0xFFFFFFFF
+    for name, v in (("lightPos", light_pos), ("lightColor", light_color), ("sky", sky)):
+        a = np.asarray(v, np.float32).reshape(-1)
+        if a.shape != (3,):
+            raise _lib.MrtError(f"path: {name} is three floats")
+        setattr(p, name, (C.c_float * 3)(*a.tolist()))
+    p.lightRadius, p.maxDist, p.compact = float(light_radius), float(max_dist), int(bool(compact))
+    return p
+
+
+def path_extend(rays, results, state, radiance, normals, material, vertex: int, depth: int, num_samples: int,
+                seed: int, light_pos, light_radius: float, light_color=(1.0, 1.0, 1.0), sky=(0.2, 0.4, 0.8),
+                max_dist: float = 1.0e30, compact: bool = True, num_slots: int | None = None) -> dict:
+    """mrth_path_extend (the CPU statement of mrt_path_extend, whose bits it gives): one vertex of
+    a batch's paths. At vertex 0 rays / results are the batch's input rays (slot i starts from
+    input i // num_samples; num_slots defaults to inputs * num_samples) and state is None; later
+    they hold one entry per slot. radiance (float32 [paths, 4]) is added to in place. Returns
+    shadow, pending, rays (None at vertex == depth) and state as arrays of num_slots entries
+    (compact: the survivors first, the rest zero) and live, the survivor count."""
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    res = np.ascontiguousarray(results).view(np.int32).reshape(-1, 4)
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    mat = np.ascontiguousarray(material).view(np.uint32).reshape(-1)
+    if radiance.dtype != np.float32 or radiance.ndim != 2 or radiance.shape[1] != 4 or not radiance.flags.c_contiguous:
+        raise _lib.MrtError("path_extend: radiance is a contiguous float32 [paths, 4] array")
+    if num_slots is None:
+        num_slots = len(r) * num_samples if vertex == 0 else len(r)
+    inputs = -(-num_slots // max(1, num_samples)) if vertex == 0 else num_slots
+    st = None if state is None else np.ascontiguousarray(state).view(np.int32).reshape(-1, 4)
+    if len(r) < inputs or len(res) < inputs or len(nrm) != len(mat) or (st is not None and len(st) < num_slots):
+        raise _lib.MrtError("path_extend: the buffers do not hold the slots")
+    p = path_params(vertex, depth, num_samples, seed, light_pos, light_radius, light_color, sky, max_dist, compact)
+    out = {"shadow": np.zeros((num_slots, 8), np.float32), "pending": np.zeros((num_slots, 4), np.float32),
+           "rays": np.zeros((num_slots, 8), np.float32) if vertex < depth else None,
+           "state": np.zeros((num_slots, 4), np.int32)}
+    live = np.full(1, -1, np.int32)
+    p.triNormals, p.triMaterialColor, p.numTris = _ptr(nrm), _ptr(mat), len(mat)
+    p.numSlots, p.numPaths = num_slots, len(radiance)
+    p.inRays, p.inResults, p.inState = _ptr(r), _ptr(res), None if st is None else _ptr(st)
+    p.outShadowRays, p.outPending, p.outState = _ptr(out["shadow"]), _ptr(out["pending"]), _ptr(out["state"])
+    p.outRays = None if out["rays"] is None else _ptr(out["rays"])
+    p.radiance, p.liveCount = _ptr(radiance), _ptr(live)
+    _lib.check_host(_lib.host_lib().mrth_path_extend(C.byref(p)))
+    out["live"] = int(live[0]) if num_slots else 0
+    return out
+
+
+def path_accumulate(state, pending, shadow_results, radiance, num_slots: int | None = None) -> np.ndarray:
+    """mrth_path_accumulate: radiance[task] += pending where the slot's shadow result has id -1,
+    over the first num_slots slots (default: all of state), in place."""
+    st = np.ascontiguousarray(state).view(np.int32).reshape(-1, 4)
+    pd = np.ascontiguousarray(pending, np.float32).reshape(-1, 4)
+    res = np.ascontiguousarray(shadow_results).view(np.int32).reshape(-1, 4)
+    n = len(st) if num_slots is None else num_slots
+    if radiance.dtype != np.float32 or radiance.ndim != 2 or radiance.shape[1] != 4 or not radiance.flags.c_contiguous:
+        raise _lib.MrtError("path_accumulate: radiance is a contiguous float32 [paths, 4] array")
+    if n > len(st) or n > len(pd) or n > len(res):
+        raise _lib.MrtError("path_accumulate: the buffers do not hold the slots")
+    _lib.check_host(_lib.host_lib().mrth_path_accumulate(n, len(radiance), _ptr(st), _ptr(pd), _ptr(res), _ptr(radiance)))
+    return radiance
+
+
+def path_resolve(num_samples: int, slot_to_id, primary_results, radiance, num_pixels: int, first_primary: int = 0,
+                 num_primary: int | None = None, pixels: np.ndarray | None = None, image: np.ndarray | None = None,
+                 want_image: bool = False):
+    """mrth_path_resolve: the batch's pixels (uint32 [num_pixels], untouched ones 0 or `pixels`'
+    own) and, with want_image or image, the unclamped float32 [num_pixels, 4] values."""
+    s2i = np.ascontiguousarray(slot_to_id, np.int32)
+    pres = np.ascontiguousarray(primary_results).view(np.int32).reshape(-1, 4)
+    rad = np.ascontiguousarray(radiance, np.float32).reshape(-1, 4)
+    if num_primary is None:
+        num_primary = len(rad) // num_samples
+    if first_primary < 0 or first_primary + num_primary > len(pres) or len(s2i) != len(pres) or \
+            len(rad) < num_primary * num_samples:
+        raise _lib.MrtError("path_resolve: the batch does not fit the primary batch")
+    if pixels is None:
+        pixels = np.zeros(num_pixels, np.uint32)
+    if image is None and want_image:
+        image = np.zeros((num_pixels, 4), np.float32)
+    _lib.check_host(_lib.host_lib().mrth_path_resolve(num_samples, first_primary, num_primary, _ptr(s2i), _ptr(pres),
+                                                      _ptr(rad), _ptr(pixels), None if image is None else _ptr(image)))
+    return (pixels, image) if image is not None else pixels
+
+
 def ray_sort(rays, slot_to_id=None, drop_levels: int = 0, box: int = 0) -> dict:
     """RayBuffer::mortonSort on the host (mrth_ray_sort; the CPU statement of
     RayBuffer.morton_sort, whose bits it reproduces): the batch in the order of the reference's

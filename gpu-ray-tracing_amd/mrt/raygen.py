@@ -205,7 +205,7 @@ class DeviceRayGen:
         return int(self.count_hits_async(rays, stream).item())
 
 
-RAY_PRIMARY, RAY_AO, RAY_DIFFUSE, RAY_SHADOW = 0, 1, 2, 3
+RAY_PRIMARY, RAY_AO, RAY_DIFFUSE, RAY_SHADOW, RAY_PATH = 0, 1, 2, 3, 4
 
 
 class DeviceReconstructor:

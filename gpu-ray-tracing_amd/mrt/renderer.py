@@ -18,6 +18,10 @@ A fourth ray type, RAY_SHADOW, runs the generator the reference wrote and never 
 (RayGen::shadow, RayGen.cc:147-183): batches of any-hit rays from the primary hits towards an area
 light, batched and seeded like AO, reconstructed by DeviceReconstructor.reconstruct_lit.
 
+A fifth, RAY_PATH, carries the same batches of primary hits through up to `depth` diffuse bounces
+with a light sample at every vertex (mrt.path.PathIntegrator): next_batch starts a
+batch's paths, trace_batch runs its vertices, update_result resolves it.
+
 The reference draws every AO/diffuse batch seed from the C library's rand()
 (RayGen.cc:106; App never seeds it, so the sequence starts at glibc's
 1804289383); GlibcRand restates glibc's TYPE_3 generator so batch k of a frame
@@ -31,10 +35,22 @@ import torch
 
 from . import _lib
 from .host import Camera, Scene
-from .raygen import RAY_AO, RAY_DIFFUSE, RAY_PRIMARY, RAY_SHADOW, DeviceRayGen, DeviceReconstructor
+from .path import PathIntegrator
+from .raygen import RAY_AO, RAY_DIFFUSE, RAY_PATH, RAY_PRIMARY, RAY_SHADOW, DeviceRayGen, DeviceReconstructor
 from .tracer import RayBuffer, Tracer
 
 MAX_BATCH_RAYS = 1 << 21   # Renderer.cc:46 m_raygen(1 << 21)
+# Whether a RAY_PATH frame compacts its live paths between vertices unless set_params says
+# otherwise. On: the compacted batch was faster than the in-place one on bunny (0.71x) and hairball
+# (0.85x) by far more than the range of three medians (profiles/path.txt).
+PATH_COMPACT_DEFAULT = True
+
+
+class _PathBatch:
+    """What Renderer.batch holds for a RAY_PATH batch: its size (paths), nothing to trace by itself."""
+
+    def __init__(self, size: int):
+        self.size = size
 
 
 class GlibcRand:
@@ -85,6 +101,9 @@ class Renderer:
         self._recon = None
         self.ray_type, self.num_samples, self.ao_radius = RAY_PRIMARY, 1, 5.0
         self.light_pos, self.light_radius = (0.0, 0.0, 0.0), 0.0
+        self.depth, self.light_color, self.sky, self.compact = 1, (1.0, 1.0, 1.0), (0.2, 0.4, 0.8), PATH_COMPACT_DEFAULT
+        self._paths: PathIntegrator | None = None
+        self.path_stats: list[int] = []   # the last path batch's live counts per vertex
         self.primary: RayBuffer | None = None
         self.slot_to_id: torch.Tensor | None = None
         self.batch: RayBuffer | None = None
@@ -101,19 +120,29 @@ class Renderer:
 
     def set_params(self, ray_type: int = RAY_PRIMARY, num_samples: int = 1, ao_radius: float = 5.0,
                    sort_secondary: bool = False, sort_drop_levels: int = 0, sort_box: int = 0,
-                   light_pos=(0.0, 0.0, 0.0), light_radius: float = 0.0) -> None:
+                   light_pos=(0.0, 0.0, 0.0), light_radius: float = 0.0, depth: int = 1,
+                   light_color=(1.0, 1.0, 1.0), sky=(0.2, 0.4, 0.8), compact: bool | None = None) -> None:
         """sort_secondary: Morton-sort every AO / diffuse / shadow batch before it is traced (the
         reference's sortSecondary); sort_drop_levels / sort_box: RayBuffer.morton_sort's drop_levels
         and box. light_pos / light_radius: the area light of a RAY_SHADOW frame (a cube of half-side
-        light_radius round light_pos, as the reference samples it); the other types ignore them."""
-        if ray_type not in (RAY_PRIMARY, RAY_AO, RAY_DIFFUSE, RAY_SHADOW):
+        light_radius round light_pos, as the reference samples it); the other types ignore them.
+        RAY_PATH also takes depth (bounces after the primary hit, 0..64), light_color, sky (what a
+        path that leaves the scene collects) and compact (None: PATH_COMPACT_DEFAULT): whether the
+        live paths are compacted between vertices or kept in place; it cannot be sorted."""
+        if ray_type not in (RAY_PRIMARY, RAY_AO, RAY_DIFFUSE, RAY_SHADOW, RAY_PATH):
             raise _lib.MrtError(f"unknown ray type {ray_type}")
-        if len(tuple(light_pos)) != 3:
-            raise _lib.MrtError("light_pos is three floats")
+        if len(tuple(light_pos)) != 3 or len(tuple(light_color)) != 3 or len(tuple(sky)) != 3:
+            raise _lib.MrtError("light_pos, light_color and sky are three floats each")
+        if ray_type == RAY_PATH and sort_secondary:
+            raise _lib.MrtError("a RAY_PATH frame's batches are not sorted (sort_secondary)")
+        if ray_type == RAY_PATH and not 0 <= int(depth) <= _lib.MRT_PATH_MAX_DEPTH:
+            raise _lib.MrtError(f"depth {depth} outside 0..{_lib.MRT_PATH_MAX_DEPTH}")
         if not 0 <= int(sort_drop_levels) <= 24 or int(sort_box) not in (0, 1):
             raise _lib.MrtError(f"sort_drop_levels {sort_drop_levels} outside 0..24 or sort_box {sort_box} outside 0..1")
         self.ray_type, self.num_samples, self.ao_radius = ray_type, int(num_samples), float(ao_radius)
         self.light_pos, self.light_radius = tuple(float(x) for x in light_pos), float(light_radius)
+        self.depth, self.compact = int(depth), PATH_COMPACT_DEFAULT if compact is None else bool(compact)
+        self.light_color, self.sky = tuple(float(x) for x in light_color), tuple(float(x) for x in sky)
         self.sort_secondary, self.sort_drop_levels, self.sort_box = bool(sort_secondary), int(sort_drop_levels), int(sort_box)
 
     def set_vertices(self, vertices, stream=None, rebuild_above: float | None = None) -> dict:
@@ -192,6 +221,9 @@ class Renderer:
         lo, hi = rng
         self._next_input = hi
         seed = self.batch_seeds(lo // self._batch_inputs() + 1)[-1]
+        if self.ray_type == RAY_PATH:
+            self._begin_paths(lo, hi, seed)
+            return True
         if self.ray_type == RAY_SHADOW:
             self.batch = self.gen.shadow(self.primary, self.num_samples, self.light_pos, self.light_radius,
                                          seed=seed, first=lo, count=hi - lo)
@@ -202,6 +234,20 @@ class Renderer:
             self.batch, self.batch_id_to_slot, _ = self.batch.morton_sort(drop_levels=self.sort_drop_levels,
                                                                           box=self.sort_box)
         return True
+
+    def _begin_paths(self, lo: int, hi: int, seed: int) -> None:
+        """Start the paths of primaries [lo, hi). self.batch becomes the batch's shadow rays of
+        vertex 0 once trace_batch has made them; until then it is a placeholder of the batch's size,
+        which is what batch_start advances by."""
+        if self._recon is None:
+            self._recon = DeviceReconstructor(self.scene)
+        if self._paths is None:
+            self._paths = PathIntegrator(self.tracer, self.gen.device)
+        self._paths.begin(self.primary, lo, hi - lo, self.num_samples, self.depth, seed, self.gen.normals,
+                          self._recon.material, self.light_pos, self.light_radius, self.light_color, self.sky,
+                          self.cam.far, self.compact)
+        self.batch = _PathBatch((hi - lo) * self.num_samples)
+        self.path_stats = self._paths.stats
 
     def _max_dist(self) -> float:
         return self.ao_radius if self.ray_type == RAY_AO else self.cam.far
@@ -230,6 +276,8 @@ class Renderer:
         the same positions of the batches. num_rays: the rays listed (mrt.dist.shard_blocks_device).
         A frame of any number of batches (any max_batch next_batch accepts): above 256 the
         generator reads the batch seeds from device scratch instead of its arguments."""
+        if self.ray_type == RAY_PATH:
+            raise _lib.MrtError("secondary_blocks: a RAY_PATH frame is not generated in blocks")
         if self.ray_type == RAY_PRIMARY or self.primary is None:
             raise _lib.MrtError("secondary_blocks needs an AO, diffuse or shadow frame (set_params, begin_frame)")
         if self.ray_type == RAY_SHADOW:
@@ -248,6 +296,8 @@ class Renderer:
         block=block_rays and priority=mrt.dist.live_priority(...) puts results back). Any
         block_rays >= 1 and any number of batches: the limit is the frame's, 2^31 - 1 rays (a
         shard of more than 16 384 blocks is ordered in tiles, with stream-ordered scratch)."""
+        if self.ray_type == RAY_PATH:
+            raise _lib.MrtError("shard: sharded RAY_PATH frames are not supported")
         if self.ray_type == RAY_PRIMARY or self.primary is None:
             raise _lib.MrtError("shard needs an AO, diffuse or shadow frame (set_params, begin_frame)")
         blocks, n = self.gen.shard_blocks(self.primary, self.num_samples, block_rays, world, rank, order, stream)
@@ -256,13 +306,20 @@ class Renderer:
     def trace_batch(self) -> float:
         if self.batch is None:
             raise _lib.MrtError("Renderer.trace_batch without a batch (call next_batch)")
+        if self.ray_type == RAY_PATH:   # every vertex of the batch: the sum of its traces' milliseconds
+            ms = self._paths.run(exact_rcp=self.exact_rcp)
+            self.path_stats = self._paths.stats
+            return ms
         return self.tracer.trace_batch(self.batch, exact_rcp=self.exact_rcp)
 
-    def update_result(self, pixels: torch.Tensor | None = None) -> torch.Tensor:
-        """reconstructKernel of the current batch into `pixels` (w*h ABGR int32)."""
+    def update_result(self, pixels: torch.Tensor | None = None, image: torch.Tensor | None = None) -> torch.Tensor:
+        """reconstructKernel of the current batch into `pixels` (w*h ABGR int32). image: a RAY_PATH
+        frame's unclamped values (float32 [w*h, 4]), optional; the other types ignore it."""
         if self._recon is None:
             self._recon = DeviceReconstructor(self.scene)
         n = 1 if self.ray_type == RAY_PRIMARY else self.num_samples
+        if self.ray_type == RAY_PATH:
+            return self._paths.resolve(self.slot_to_id, self.w * self.h, pixels=pixels, image=image)
         if self.ray_type == RAY_SHADOW:   # the generator's normals: the ones set_vertices keeps current
             return self._recon.reconstruct_lit(self.primary, self.slot_to_id, self.w * self.h, self.batch, n,
                                                self.gen.normals, self.light_pos, pixels=pixels,

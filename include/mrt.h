@@ -752,8 +752,9 @@ int  mrt_ray_sort(const void* inRays, const int32_t* inSlotToId /* NULL = identi
 int  mrt_count_hits(const void* results, int32_t numRays, int32_t* hitCount, void* stream);
 
 /* ray types of a batch (reference RayType_Primary / _AO / _Diffuse, App.cc); MRT_RAY_SHADOW is
- * the frame type of mrt_raygen_shadow / mrt_reconstruct_lit below (mrt_reconstruct refuses it) */
-enum { MRT_RAY_PRIMARY = 0, MRT_RAY_AO = 1, MRT_RAY_DIFFUSE = 2, MRT_RAY_SHADOW = 3 };
+ * the frame type of mrt_raygen_shadow / mrt_reconstruct_lit below, MRT_RAY_PATH that of
+ * mrt_path_extend / _accumulate / _resolve (mrt_reconstruct refuses both) */
+enum { MRT_RAY_PRIMARY = 0, MRT_RAY_AO = 1, MRT_RAY_DIFFUSE = 2, MRT_RAY_SHADOW = 3, MRT_RAY_PATH = 4 };
 
 /* reconstructKernel (RendererKernels.cu:60-108; ReconstructInput RendererKernels.hh:46-61,
  * filled by Renderer.cc:421-445): one ABGR pixel per primary ray of the batch, at
@@ -825,6 +826,130 @@ int  mrt_reconstruct_lit(int32_t numRaysPerPrimary, int32_t firstPrimary, int32_
                          const int32_t* primarySlotToId, const void* primaryRays, const void* primaryResults,
                          const int32_t* batchIdToSlot, const void* batchResults, const float* triNormals,
                          const uint32_t* triMaterialColor, const float light[3], uint32_t* pixels, void* stream);
+
+/* ---- multi-bounce diffuse paths with light sampling at every vertex ----
+ * A path frame (MRT_RAY_PATH) carries S paths per primary ray through vertices 0 (the primary hit)
+ * to depth. A path is one record per buffer at its SLOT: its current ray (Ray, 32 B), that ray's
+ * result (RayResult, 16 B), and a 16-byte state {float throughput[3]; int32 task}. task is the path's
+ * index in its batch, input ray * S + sample s, and names its entry of `radiance` (4 floats per
+ * path: r, g, b, one unused). The caller zeroes radiance before vertex 0 and drives, per vertex b:
+ *     mrt_path_extend(b)  ->  an any-hit trace of the shadow rays  ->  mrt_path_accumulate
+ *                         ->  (b < depth) a closest-hit trace of the bounce rays  ->  b + 1
+ * over *liveCount slots each, then mrt_path_resolve. All three are stream-ordered with no host sync.
+ *
+ * mrt_path_extend, slot i < numSlots. At vertex 0 the path is started: ray and result are
+ * inRays / inResults[i / S] (the batch's input rays; no replicated copy is made), throughput
+ * (1, 1, 1), task i; inState is not read. At vertex >= 1 ray, result and state are entry i of
+ * inRays / inResults / inState, and a state whose task lies outside [0, numPaths) is no path: the
+ * slot is dead and adds nothing. With (id, t) the result:
+ *   - Miss: id outside [0, numTris) (so id -1). At vertex >= 1 radiance[task] += throughput * sky,
+ *     channel by channel; at vertex 0 nothing is added (mrt_path_resolve writes the background where
+ *     the primary's id is -1). The path ends.
+ *   - Hit: the path survives. x = o + d * max(t - 1e-4, 0) (mrt_raygen_shadow's origin); nf =
+ *     triNormals[id] turned against the ray (negated where dot(n, d) > 0); albedo = the first three
+ *     channels of triMaterialColor[id] through the device fromABGR (byte * (1 / 255));
+ *     throughput *= albedo.
+ *   - Hash words: (a, b, c) = jenkinsMix twice over (seed + vertex * 0x9e3779b9 + key, 0x9e3779b9,
+ *     0x9e3779b9) in uint32, key = i / S (the input ray's index) at vertex 0, so that a pixel's S
+ *     paths share the offset and stay stratified, and key = task at vertex >= 1. A third jenkinsMix
+ *     of the same three words gives (a', b', .).
+ *   - Light sample: the shadow ray is mrt_raygen_shadow's ray for origin x, sample s of S and the
+ *     offset (a, b, c) * 2^-32 (converted round-to-nearest, so an offset of exactly 1 occurs),
+ *     towards the cube of half-side lightRadius round lightPos; tmax = the distance to the sample.
+ *     At vertex 0 it is bit for bit the ray mrt_raygen_shadow makes for that input, sample and seed.
+ *     Its pending contribution is throughput * lightColor * k per channel (in that order), k =
+ *     mrt_reconstruct_lit's max(dot(nf, l), 0) towards the light's CENTRE: as there, the centre
+ *     stands for the light and there is no distance falloff.
+ *   - Bounce ray, only where vertex < depth: (h1, h2) = the Halton (2, 3) point of index s as
+ *     mrt_raygen_ao computes it (radical inverses of s + 1); u1 = h1 + a' * 2^-32, u2 = h2 + b' * 2^-32,
+ *     each wrapped once (`if (p >= 1) p -= 1`). cos and sin of 2 pi u2 without libm: v = 4 * u2,
+ *     q = (int)v, f = v - q; where f > 0.5: f = f - 1, q = q + 1 (all exact); with g = f * f,
+ *       S = f * (s1 + g * (s3 + g * (s5 + g * (s7 + g * s9)))),
+ *       C = 1 + g * (c2 + g * (c4 + g * (c6 + g * (c8 + g * c10)))),
+ *     s1.. = 1.5707963267948966, -0.6459640975062462, 0.07969262624616703, -0.004681754135318687,
+ *     0.00016044118478735975 and c2.. = -1.2337005501361697, 0.253669507901048, -0.020863480763352957,
+ *     0.0009192602748394263, -2.5202042373060596e-05 (the Taylor terms (pi/2)^k / k!, rounded to
+ *     float32), and (cos, sin) = (C, S), (-S, C), (-C, -S), (S, -C) for q & 3 = 0, 1, 2, 3; within
+ *     1e-6 of the true values (measured: DESIGN section 15). r = sqrt(u1), x = r * cos, y = r * sin,
+ *     z = sqrt(max(1 - x * x - y * y, 0)). The tangents are mrt_raygen_ao's perp / biperp of nf
+ *     (perp = (nf.y, -nf.x, 0), or (0, nf.z, -nf.y) where |nf.z| is the largest component, else
+ *     (-nf.z, 0, nf.x) where |nf.x| is; normalized; biperp = cross(nf, perp)) WITHOUT its hash rotation:
+ *     the shift already rotates. direction = normalize(perp * x + biperp * y + nf * z), origin x,
+ *     tmin 0, tmax maxDist.
+ * Estimator: cosine-weighted sampling of a Lambertian surface cancels the cosine and the 1 / pi, so
+ * a bounce leaves throughput *= albedo and nothing else. Light and sky are in the units of
+ * mrt_reconstruct_lit's k * v and of the background colour, not radiometric ones.
+ * Output. compact != 0: survivor i's shadow ray, pending contribution (4 floats: r, g, b, 0), bounce
+ * ray and new state go to entry rank(i) of outShadowRays / outPending / outRays / outState, rank(i)
+ * = the number of survivors before i: stable order, the same from run to run, dense batches for both
+ * traces. compact == 0 (in-place): every slot keeps its place; a slot that holds no survivor gets
+ * rays with tmax -1 (all else 0), the state {0, 0, 0, task -1} and a zero pending, stays dead at
+ * later vertices, and the caller goes on with numSlots slots. Both modes do the same arithmetic per
+ * path: the radiance bits are equal. *liveCount (device int32) = the survivors, in both modes. In
+ * compact mode every state of a vertex >= 1 must be a path (as the previous call left them). outRays
+ * may be NULL at vertex == depth, where no bounce ray is written. Three launches, none waiting on
+ * another workgroup: a count per 256 slots, a one-workgroup scan of the counts, the step itself; the
+ * counts are scratch taken and returned on the stream (hipMallocAsync / hipFreeAsync; a failed
+ * allocation is MRT_ERR_HIP).
+ * Parity: the arithmetic is csrc/path_common.hpp's on both sides and this part of the library is
+ * built like mrt_raygen_shadow's, so every output equals mrth_path_extend's (mrt_host.h) bit for
+ * bit; only the bits of a NaN that an operation makes differ.
+ * Checks, in this order, nothing written where one fails: NULL params; a negative numSlots or
+ * numPaths, numSamples < 1, depth < 0 or vertex outside [0, depth] is MRT_ERR_INVALID_ARG; depth
+ * above 64 or more than 2^22 slots or paths MRT_ERR_TOO_LARGE; numPaths < numSlots at vertex 0
+ * MRT_ERR_INVALID_ARG; numSlots == 0 returns MRT_OK and launches nothing; then
+ * MRT_ERR_INVALID_ARG for a NULL required pointer (all but inState at vertex 0 and outRays at
+ * vertex == depth), numTris < 0, a ray buffer, state or pending buffer that is not 16-byte aligned,
+ * or an output buffer that overlaps an input buffer or another output. */
+typedef struct mrt_path_extend_params {
+    int32_t vertex;              /* 0..depth */
+    int32_t depth;               /* 0..64 */
+    int32_t numSamples;          /* S */
+    uint32_t seed;               /* the batch's */
+    float lightPos[3];
+    float lightRadius;
+    float lightColor[3];
+    float sky[3];
+    float maxDist;               /* a bounce ray's tmax */
+    int32_t compact;
+    const float* triNormals;     /* 3 floats per triangle */
+    const uint32_t* triMaterialColor;
+    int64_t numTris;
+    int32_t numSlots;
+    int32_t numPaths;            /* entries of radiance */
+    const void* inRays;
+    const void* inResults;
+    const void* inState;
+    void* outShadowRays;
+    void* outPending;
+    void* outRays;
+    void* outState;
+    float* radiance;
+    int32_t* liveCount;
+} mrt_path_extend_params;
+int  mrt_path_extend(const mrt_path_extend_params* params, void* stream);
+
+/* After the shadow batch of a vertex is traced: radiance[task] += pending[i], channel by channel,
+ * for every slot i < numSlots whose state's task lies in [0, numPaths) and whose shadow result has
+ * id -1 (the ray reached its light sample). A path's additions thus happen in vertex order, each by
+ * the one lane that holds the path: no float atomics, whose order would not be defined. Equals
+ * mrth_path_accumulate bit for bit. numSlots == 0 returns MRT_OK and launches nothing; a negative
+ * count, a NULL pointer or a state / pending / radiance buffer that is not 16-byte aligned is
+ * MRT_ERR_INVALID_ARG, more than 2^22 slots or paths MRT_ERR_TOO_LARGE, and nothing is written. */
+int  mrt_path_accumulate(int32_t numSlots, int32_t numPaths, const void* state, const void* pending,
+                         const void* shadowResults, float* radiance, void* stream);
+
+/* A path batch's pixels: per primary ray i < numPrimary of the batch, at pixel =
+ * primarySlotToId[firstPrimary + i]: value = (sum of radiance[i * numSamples + s] over s in sample
+ * order, from 0) * (1 / numSamples) per channel, alpha 1; pixels[pixel] = the value through the
+ * truncating device toABGR; image (may be NULL; 4 floats per pixel, 16-byte aligned) gets the
+ * unclamped value. Where primaryResults[firstPrimary + i] has id -1 the value is the background
+ * (0.2, 0.4, 0.8, 1). Equals mrth_path_resolve bit for bit. numPrimary == 0 returns MRT_OK and
+ * launches nothing; a bad shape or a NULL required pointer is MRT_ERR_INVALID_ARG, more than 2^22
+ * paths MRT_ERR_TOO_LARGE, and nothing is written. */
+int  mrt_path_resolve(int32_t numSamples, int32_t firstPrimary, int32_t numPrimary, const int32_t* primarySlotToId,
+                      const void* primaryResults, const float* radiance, uint32_t* pixels, float* image,
+                      void* stream);
 
 /* ---- a moving scene: normals, colours and the tree's cost on the device ---- */
 /* Scene::Scene's per-triangle tables (reference Scene.cc:37,66-80) from vertices in DEVICE

@@ -216,6 +216,44 @@ int  mrth_reconstruct_lit(int32_t numRaysPerPrimary, int32_t firstPrimary, int32
                           const float* triNormals, const uint32_t* triMaterialColor, const float light[3],
                           uint32_t* pixels);
 
+/* The CPU statements of mrt_path_extend, mrt_path_accumulate and mrt_path_resolve (mrt.h, which
+ * states the arithmetic, the compaction and the checks), with the same arguments over HOST memory
+ * and no stream, built from the same header (csrc/path_common.hpp): the same bits in every output,
+ * the live count included. The struct is mrt_path_extend_params, field for field. Where mrt.h says
+ * MRT_ERR_INVALID_ARG or MRT_ERR_TOO_LARGE these return MRTH_ERR_INVALID_ARG; alignment and overlap,
+ * which matter to the device's 16-byte accesses and parallel lanes only, are not checked here. */
+typedef struct mrth_path_extend_params {
+    int32_t vertex;
+    int32_t depth;
+    int32_t numSamples;
+    uint32_t seed;
+    float lightPos[3];
+    float lightRadius;
+    float lightColor[3];
+    float sky[3];
+    float maxDist;
+    int32_t compact;
+    const float* triNormals;
+    const uint32_t* triMaterialColor;
+    int64_t numTris;
+    int32_t numSlots;
+    int32_t numPaths;
+    const void* inRays;
+    const void* inResults;
+    const void* inState;
+    void* outShadowRays;
+    void* outPending;
+    void* outRays;
+    void* outState;
+    float* radiance;
+    int32_t* liveCount;
+} mrth_path_extend_params;
+int  mrth_path_extend(const mrth_path_extend_params* params);
+int  mrth_path_accumulate(int32_t numSlots, int32_t numPaths, const void* state, const void* pending,
+                          const void* shadowResults, float* radiance);
+int  mrth_path_resolve(int32_t numSamples, int32_t firstPrimary, int32_t numPrimary, const int32_t* primarySlotToId,
+                       const void* primaryResults, const float* radiance, uint32_t* pixels, float* image);
+
 /* RayBuffer::mortonSort (RayBuffer.cc:256-324): the CPU statement of mrt_ray_sort (mrt.h, which
  * states the key and the order), with the same arguments over HOST memory and no stream. outBox
  * is six host floats (lo.xyz, hi.xyz). The box and the keys are csrc/raysort_common.hpp's on both

@@ -12,10 +12,15 @@ trace time, App.cc:204).
       --camera "6omr/04j3200bR6Z/0/3ZEAz/x4smy19///c/05frY109Qx7w////m100"
   python tools/render_frame.py --scene bunny --ray-type shadow --samples 16 --light 0.2 1.5 2.0 \
       --light-radius 0.2
+  python tools/render_frame.py --scene bunny --ray-type path --samples 8 --depth 4 --sky 0.2 0.4 0.8
 
 --ray-type shadow lights the frame from an area light (--light x y z, --light-radius r: a cube of
 half-side r, as the reference's shadow generator samples it); without --light the light sits at
-(0.5, 0.9, 0.9) of the scene's box with a radius of a fiftieth of its diagonal.
+(0.5, 0.9, 0.9) of the scene's box with a radius of a fiftieth of its diagonal. --ray-type path
+carries every primary hit through up to --depth diffuse bounces with a sample of that light at every
+vertex (--light-color r g b) and --sky r g b for the paths that leave the scene; --compact / --in-place
+choose whether live paths are compacted between vertices (default: the Renderer's). Its rate counts
+the paths started, over the summed time of all its traces.
 """
 from __future__ import annotations
 
@@ -30,11 +35,11 @@ sys.path.insert(0, os.path.join(REPO, "gpu-ray-tracing_amd"))
 import torch  # noqa: E402
 
 import mrt  # noqa: E402
-from mrt.raygen import RAY_AO, RAY_DIFFUSE, RAY_PRIMARY, RAY_SHADOW  # noqa: E402
+from mrt.raygen import RAY_AO, RAY_DIFFUSE, RAY_PATH, RAY_PRIMARY, RAY_SHADOW  # noqa: E402
 from mrt.renderer import Renderer  # noqa: E402
 from mrt.tracer import GpuBvh, Tracer  # noqa: E402
 
-TYPES = {"primary": RAY_PRIMARY, "ao": RAY_AO, "diffuse": RAY_DIFFUSE, "shadow": RAY_SHADOW}
+TYPES = {"primary": RAY_PRIMARY, "ao": RAY_AO, "diffuse": RAY_DIFFUSE, "shadow": RAY_SHADOW, "path": RAY_PATH}
 
 
 def main() -> int:
@@ -45,8 +50,16 @@ def main() -> int:
     ap.add_argument("--ao-radius", type=float, default=None, help="the App's --ao-radius (default: the scene's)")
     ap.add_argument("--ray-type", choices=sorted(TYPES), default="primary")
     ap.add_argument("--samples", type=int, default=8)
-    ap.add_argument("--light", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="shadow: the light's centre")
-    ap.add_argument("--light-radius", type=float, default=None, help="shadow: half the side of the light's cube")
+    ap.add_argument("--light", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="shadow, path: the light's centre")
+    ap.add_argument("--light-radius", type=float, default=None, help="shadow, path: half the side of the light's cube")
+    ap.add_argument("--light-color", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("R", "G", "B"), help="path")
+    ap.add_argument("--sky", type=float, nargs=3, default=(0.2, 0.4, 0.8), metavar=("R", "G", "B"),
+                    help="path: what a path that leaves the scene collects")
+    ap.add_argument("--depth", type=int, default=4, help="path: bounces after the primary hit (0..64)")
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--compact", dest="compact", action="store_true", default=None,
+                      help="path: compact the live paths between vertices")
+    mode.add_argument("--in-place", dest="compact", action="store_false", help="path: keep every path at its slot")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--out", default="gpurun_out/frame.ppm")
@@ -64,26 +77,28 @@ def main() -> int:
     w, h, rt = a.width, a.height, TYPES[a.ray_type]
     r = Renderer(tracer, scene)
     light, light_radius = a.light, a.light_radius
-    if rt == RAY_SHADOW and (light is None or light_radius is None):
+    if rt in (RAY_SHADOW, RAY_PATH) and (light is None or light_radius is None):
         v, _, _ = scene.arrays()
         lo, hi = v.min(axis=0).astype(float), v.max(axis=0).astype(float)
         light = light if light is not None else [float(x) for x in lo + (hi - lo) * (0.5, 0.9, 0.9)]
         light_radius = light_radius if light_radius is not None else float(0.02 * ((hi - lo) ** 2).sum() ** 0.5)
     r.set_params(rt, 1 if rt == RAY_PRIMARY else a.samples, ao_radius, light_pos=light or (0.0, 0.0, 0.0),
-                 light_radius=light_radius or 0.0)
+                 light_radius=light_radius or 0.0, depth=a.depth, light_color=a.light_color, sky=a.sky, compact=a.compact)
     r.begin_frame(cam, w, h)
     counted = r.total_num_rays()
     pixels = torch.zeros(w * h, dtype=torch.int32, device="cuda")
-    ms, batches = 0.0, 0
+    ms, batches, live = 0.0, 0, None
     while r.next_batch():
         ms += r.trace_batch()
         r.update_result(pixels)
         batches += 1
+        live = list(r.path_stats) if rt == RAY_PATH else None
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     mrt.write_ppm(a.out, pixels.cpu().numpy(), w, h)
     print(json.dumps({"scene": a.obj or a.scene, "camera": a.camera, "ray_type": a.ray_type, "width": w, "height": h,
-                      "samples": r.num_samples, "light": light, "light_radius": light_radius, "batches": batches, "trace_ms": round(ms, 4), "rays_counted": counted,
+                      "samples": r.num_samples, "light": light, "light_radius": light_radius, "batches": batches,
+                      **({"depth": a.depth, "compact": r.compact, "live_last_batch": live} if rt == RAY_PATH else {}), "trace_ms": round(ms, 4), "rays_counted": counted,
                       "mrays_per_s": round(counted / ms / 1e3, 2) if ms > 0 else None, "image": a.out}))
     return 0
 
