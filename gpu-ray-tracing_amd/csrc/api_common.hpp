@@ -1,5 +1,5 @@
 // api_common.hpp — what the C-ABI files (mrt_api.cpp, bind_api.cpp, refit_api.cpp, build_api.cpp,
-// derive_api.cpp, frame_api.cpp, scene_api.cpp, light_api.cpp, path_api.cpp, compat_api.cpp) share: the error returns, the device guard, and the owners of
+// derive_api.cpp, frame_api.cpp, scene_api.cpp, light_api.cpp, path_api.cpp, denoise_api.cpp, compat_api.cpp) share: the error returns, the device guard, and the owners of
 // the device memory, the stream-ordered scratch and the events the library allocates.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -110,6 +110,18 @@ class PathExtendParams(C.Structure):
                 ("outRays", vp), ("outState", vp), ("radiance", vp), ("liveCount", vp)]
 
 
+class DenoiseParams(C.Structure):
+    """mrt_denoise_params / mrth_denoise_params (one layout)."""
+    _fields_ = [("width", i32), ("height", i32), ("iterations", i32), ("normalSquarings", i32), ("sigmaColor", f32),
+                ("sigmaPlane", f32), ("variant", i32), ("reserved", i32), ("image", vp), ("guide", vp), ("albedo", vp), ("scratch", vp * 2), ("imageOut", vp),
+                ("pixels", vp)]
+
+
+MRT_DENOISE_MAX_PIXELS = 1 << 26    # csrc/denoise_limits.hpp
+MRT_DENOISE_MAX_ITERATIONS = 8
+MRT_DENOISE_MAX_SQUARINGS = 10
+MRT_DENOISE_TILE = (32, 8)          # the direct filter workgroup's pixels: width, height
+MRT_DENOISE_ROW_TILE = (64, 4)      # the LDS-staged one's: columns, rows a step apart
 MRT_PATH_MAX_PATHS = 1 << 22    # csrc/path_limits.hpp
 MRT_PATH_MAX_DEPTH = 64
 MRT_PATH_SCAN_ROUND_SLOTS = 1024 * 256   # slots whose workgroup counts fill one round of the scan
@@ -219,6 +231,8 @@ TRACE_SYMBOLS = [
     ("mrt_path_extend", i32, [C.POINTER(PathExtendParams), vp]),
     ("mrt_path_accumulate", i32, [i32, i32, vp, vp, vp, vp, vp]),
     ("mrt_path_resolve", i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    ("mrt_denoise_features", i32, [i32, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]),
+    ("mrt_denoise_filter", i32, [C.POINTER(DenoiseParams), vp]),
     ("mrt_selftest_exact_rcp", i32, [C.POINTER(C.c_uint64)]),
     ("bind_CudaBVHTexture", None, [vp, i64, vp, i64, vp, i64]),
     ("unbind_CudaBVHTexture", None, []),
@@ -275,6 +289,8 @@ HOST_SYMBOLS = [
     ("mrth_path_extend", i32, [C.POINTER(PathExtendParams)]),
     ("mrth_path_accumulate", i32, [i32, i32, vp, vp, vp, vp]),
     ("mrth_path_resolve", i32, [i32, i32, i32, vp, vp, vp, vp, vp]),
+    ("mrth_denoise_features", i32, [i32, vp, vp, vp, vp, vp, i64, i32, vp, vp]),
+    ("mrth_denoise_filter", i32, [C.POINTER(DenoiseParams)]),
     ("mrth_ray_sort", i32, [vp, vp, i32, C.POINTER(RaySortParams), vp, vp, vp, vp, vp]),
     ("mrth_last_error", C.c_char_p, []),
 ]

@@ -492,6 +492,56 @@ def path_resolve(num_samples: int, slot_to_id, primary_results, radiance, num_pi
     return (pixels, image) if image is not None else pixels
 
 
+def denoise_features(slot_to_id, primary_rays, primary_results, normals, material, num_pixels: int,
+                     guide: np.ndarray | None = None, albedo: np.ndarray | None = None):
+    """mrth_denoise_features (the CPU statement of mrt_denoise_features, whose bits it gives): the
+    guide records (float32 [num_pixels, 8]: normal, hit flag, position, 0) and albedos (float32
+    [num_pixels, 4]) of a traced primary batch, at slot_to_id's pixels. Pixels no slot names keep
+    what `guide` / `albedo` held (zeros where none is passed)."""
+    s2i = np.ascontiguousarray(slot_to_id, np.int32).reshape(-1)
+    r = np.ascontiguousarray(primary_rays, np.float32).reshape(-1, 8)
+    res = np.ascontiguousarray(primary_results).view(np.int32).reshape(-1, 4)
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    mat = np.ascontiguousarray(material).view(np.uint32).reshape(-1)
+    if len(r) != len(s2i) or len(res) != len(s2i) or len(nrm) != len(mat):
+        raise _lib.MrtError("denoise_features: one ray and one result per slot, one normal per colour")
+    if guide is None:
+        guide = np.zeros((num_pixels, 8), np.float32)
+    if albedo is None:
+        albedo = np.zeros((num_pixels, 4), np.float32)
+    for name, a, cols in (("guide", guide, 8), ("albedo", albedo, 4)):
+        if a.dtype != np.float32 or a.shape != (num_pixels, cols) or not a.flags.c_contiguous:
+            raise _lib.MrtError(f"denoise_features: {name} is a contiguous float32 [{num_pixels}, {cols}] array")
+    _lib.check_host(_lib.host_lib().mrth_denoise_features(len(s2i), _ptr(s2i), _ptr(r), _ptr(res), _ptr(nrm), _ptr(mat),
+                                                          len(mat), num_pixels, _ptr(guide), _ptr(albedo)))
+    return guide, albedo
+
+
+def denoise_filter(image, guide, albedo, width: int, height: int, iterations: int = 5, sigma_color: float = 1.0,
+                   sigma_plane: float = 1.0, normal_squarings: int = 7, want_image: bool = True,
+                   want_pixels: bool = True):
+    """mrth_denoise_filter (the CPU statement of mrt_denoise_filter, whose bits it gives): the
+    a-trous filter over a width x height float image. Returns (image_out float32 [w*h, 4] or None,
+    pixels uint32 [w*h] or None)."""
+    n = int(width) * int(height)
+    img = np.ascontiguousarray(image, np.float32).reshape(-1, 4)
+    gd = np.ascontiguousarray(guide, np.float32).reshape(-1, 8)
+    alb = np.ascontiguousarray(albedo, np.float32).reshape(-1, 4)
+    if width < 1 or height < 1 or len(img) != n or len(gd) != n or len(alb) != n:
+        raise _lib.MrtError("denoise_filter: image, guide and albedo hold one entry per pixel of the frame")
+    p = _lib.DenoiseParams()
+    p.width, p.height, p.iterations, p.normalSquarings = int(width), int(height), int(iterations), int(normal_squarings)
+    p.sigmaColor, p.sigmaPlane = float(np.float32(sigma_color)), float(np.float32(sigma_plane))
+    scratch = [np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)]
+    out = np.zeros((n, 4), np.float32) if want_image else None
+    pixels = np.zeros(n, np.uint32) if want_pixels else None
+    p.image, p.guide, p.albedo = _ptr(img), _ptr(gd), _ptr(alb)
+    p.scratch[0], p.scratch[1] = _ptr(scratch[0]), _ptr(scratch[1])
+    p.imageOut, p.pixels = (None if out is None else _ptr(out)), (None if pixels is None else _ptr(pixels))
+    _lib.check_host(_lib.host_lib().mrth_denoise_filter(C.byref(p)))
+    return out, pixels
+
+
 def ray_sort(rays, slot_to_id=None, drop_levels: int = 0, box: int = 0) -> dict:
     """RayBuffer::mortonSort on the host (mrth_ray_sort; the CPU statement of
     RayBuffer.morton_sort, whose bits it reproduces): the batch in the order of the reference's

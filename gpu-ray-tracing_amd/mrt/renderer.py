@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .denoise import SIGMA_PLANE_FRACTION_DEFAULT, Denoiser
 from .host import Camera, Scene
 from .path import PathIntegrator
 from .raygen import RAY_AO, RAY_DIFFUSE, RAY_PATH, RAY_PRIMARY, RAY_SHADOW, DeviceRayGen, DeviceReconstructor
@@ -104,6 +105,8 @@ class Renderer:
         self.depth, self.light_color, self.sky, self.compact = 1, (1.0, 1.0, 1.0), (0.2, 0.4, 0.8), PATH_COMPACT_DEFAULT
         self._paths: PathIntegrator | None = None
         self.path_stats: list[int] = []   # the last path batch's live counts per vertex
+        self._denoiser: Denoiser | None = None   # made by the first denoise()
+        self._diagonal: float | None = None      # of the scene's box, for denoise's default sigma_plane
         self.primary: RayBuffer | None = None
         self.slot_to_id: torch.Tensor | None = None
         self.batch: RayBuffer | None = None
@@ -328,6 +331,32 @@ class Renderer:
         return self._recon.reconstruct(self.ray_type, self.primary, self.slot_to_id, self.w * self.h, self.batch,
                                        num_samples=n, pixels=pixels, first_primary=self.batch_start // n,
                                        batch_id_to_slot=self.batch_id_to_slot)
+
+    def denoise(self, image: torch.Tensor, pixels: torch.Tensor | None = None, image_out: torch.Tensor | None = None,
+                sigma_plane: float | None = None, stream=None, **settings):
+        """The edge-avoiding wavelet filter (mrt.denoise.Denoiser) over a RAY_PATH frame's
+        float image, called after the frame's last update_result(pixels, image=image): the denoised
+        frame goes to pixels (w*h ABGR int32) and / or image_out (float32 [w*h, 4], not `image`
+        itself); returns (pixels, image_out). The guide comes from the frame's own primary batch
+        and the current normals and colours, so a frame after set_vertices is guided by the moved
+        scene. settings: Denoiser.run's iterations, sigma_color and normal_squarings. sigma_plane
+        None: SIGMA_PLANE_FRACTION_DEFAULT of the diagonal of the scene's box (of its vertices as
+        loaded). Nothing waits on the host."""
+        if self.ray_type != RAY_PATH:
+            raise _lib.MrtError("Renderer.denoise: only a RAY_PATH frame is denoised")
+        if self.primary is None or self._recon is None:
+            raise _lib.MrtError("Renderer.denoise before begin_frame and the frame's batches")
+        if self._denoiser is None:
+            self._denoiser = Denoiser(self.gen.device)
+        if sigma_plane is None:
+            if self._diagonal is None:
+                v = self.scene.arrays()[0].astype(np.float64)
+                self._diagonal = float(np.linalg.norm(v.max(axis=0) - v.min(axis=0))) if len(v) else 1.0
+            sigma_plane = max(self._diagonal, 1.0e-30) * SIGMA_PLANE_FRACTION_DEFAULT
+        self._denoiser.set_frame(self.primary, self.slot_to_id, self.gen.normals, self._recon.material, self.w, self.h,
+                                 stream=stream)
+        return self._denoiser.run(image, pixels=pixels, image_out=image_out, sigma_plane=sigma_plane, stream=stream,
+                                  **settings)
 
     def batches(self):
         """Every batch of the frame (generated, not traced) as (RayBuffer, first ray) pairs."""

@@ -951,6 +951,93 @@ int  mrt_path_resolve(int32_t numSamples, int32_t firstPrimary, int32_t numPrima
                       const void* primaryResults, const float* radiance, uint32_t* pixels, float* image,
                       void* stream);
 
+/* ---- an edge-avoiding wavelet denoiser for path frames ----
+ * An a-trous filter (Dammertz et al. 2010) over the float image mrt_path_resolve writes, run on the
+ * albedo-demodulated image and guided by the primary hit's normal and position. Two calls: the
+ * features of a frame's traced primary batch, then the filter. All arithmetic is float32, one IEEE
+ * operation at a time in the order written here, with no fused multiply-add, no flushed denormal,
+ * correctly rounded `/` and no libm call. dot(a, b) = ((0 + a.x * b.x) + a.y * b.y) + a.z * b.z.
+ *
+ * mrt_denoise_features, one lane per primary slot i < numPrimary: p = primarySlotToId[i]; a slot
+ * whose p lies outside [0, numPixels) is skipped, nothing is read or written for it. With the
+ * slot's ray (o, d) = primaryRays[i] and result (id, t) = primaryResults[i]:
+ *   - Miss (id outside [0, numTris)): guide[p] = {0, 0, 0, 0, 0, 0, 0, 0}, albedo[p] = (1, 1, 1, 1).
+ *   - Hit: nf = triNormals[id], negated where dot(nf, d) > 0 (mrt_path_extend's rule); x = o + d * t
+ *     per component (one multiply, one add, no back-off); guide[p] = {nf.x, nf.y, nf.z, 1, x.x, x.y,
+ *     x.z, 0} (8 floats, 32 bytes); albedo[p] = the first three channels of triMaterialColor[id]
+ *     through the device fromABGR (byte * (1 / 255)), w = 1.
+ * Pixels no slot names keep what guide and albedo held. Two slots that name one pixel are the
+ * caller's error: the result is one of the two. Equals mrth_denoise_features bit for bit.
+ * Checks, in this order, nothing written where one fails: a negative numPrimary, numTris or
+ * numPixels is MRT_ERR_INVALID_ARG; more than 2^26 slots or pixels MRT_ERR_TOO_LARGE; numPrimary == 0
+ * or numPixels == 0 returns MRT_OK and launches nothing; then MRT_ERR_INVALID_ARG for a NULL pointer
+ * (the two tables may be NULL where numTris == 0), rays, results, guide or albedo not 16-byte
+ * aligned, or guide or albedo overlapping an input or each other. */
+int  mrt_denoise_features(int32_t numPrimary, const int32_t* primarySlotToId, const void* primaryRays,
+                          const void* primaryResults, const float* triNormals, const uint32_t* triMaterialColor,
+                          int64_t numTris, int32_t numPixels, void* guide, float* albedo, void* stream);
+
+/* mrt_denoise_filter over a width x height frame, pixel p = y * width + x, hit(p) = guide[p].w != 0
+ * (n_p, x_p: the guide's normal and position; image, albedo, scratch, imageOut: 4 floats per pixel).
+ *  1. Demodulate: where hit(p), per channel r, g, b: c0 = (albedo > 0) ? image / albedo : 0; at a
+ *     miss c0 = image. Channel w is carried unchanged from image to imageOut and takes no part.
+ *  2. Iterations k = 0 .. iterations - 1 with step s = 1 << k. A miss pixel copies c_k to c_{k+1}.
+ *     At a hit pixel p = (x, y): sum = (0, 0, 0), wsum = 0; for dy = -2 .. 2 (outer) and dx = -2 .. 2
+ *     (inner), both ascending, q = (x + dx * s, y + dy * s); a tap whose q lies outside the frame or
+ *     with !hit(q) is skipped; otherwise, the centre tap (dx = dy = 0) included:
+ *         hw  = h[|dx|] * h[|dy|],  h = {0.375, 0.25, 0.0625}
+ *         a   = dot(n_p, n_q);  a = (a > 0) ? a : 0  (a NaN becomes 0);  then a = a * a,
+ *               normalSquarings times (7: the exponent 128)
+ *         dpl = dot(n_p, x_q - x_p) * invPlane  (the difference per component);  wz = 1 / (1 + dpl * dpl)
+ *         e   = c_k(q) - c_k(p);  dc2 = (e.x * e.x + e.y * e.y) + e.z * e.z;  wc = 1 / (1 + dc2 * invColor2[k])
+ *         w   = ((hw * a) * wz) * wc;  sum += w * c_k(q) per channel (a multiply, then an add);  wsum += w
+ *     c_{k+1}(p) = (wsum > 0) ? sum / wsum : c_k(p). The guard covers a degenerate triangle's zero
+ *     normal (every weight 0) and a NaN weight sum.
+ *  3. Remodulate: r = hit(p) ? c_N * albedo : c_N per channel; imageOut[p] = (r, image[p].w) where
+ *     imageOut is given; pixels[p] = (r, 1) through the truncating device toABGR, as
+ *     mrt_path_resolve's, where pixels is given.
+ * Constants, computed once in float32: invPlane = 1 / sigmaPlane; invColor2[k] = 1 / (s_k * s_k) with
+ * s_k = sigmaColor * 2^-k. A sigmaColor whose square overflows gives invColor2 = 0 (wc = 1: colour
+ * takes no part); one whose square underflows to 0 gives infinity, the centre tap's 0 * infinity a
+ * NaN weight, and the pixel keeps c_k. There is no exp and no pow.
+ * One launch per iteration, each reading one image and writing another, so no workgroup waits on
+ * another and there are no float atomics; demodulation is folded into the first launch's loads,
+ * remodulation and the pixel write into the last launch's stores; iterations == 0 is one launch
+ * of steps 1 and 3. Iteration k < iterations - 1 writes scratch[k & 1]: scratch[0] is needed from 2
+ * iterations on, scratch[1] from 3 on; one that is not needed is ignored and may be NULL. Both calls
+ * are stream-ordered, with no host sync, no readback and no allocation. A launch runs one of two
+ * kernels with the same arithmetic: one loads every tap from global memory, one stages a tile of 64
+ * columns by 4 rows a step apart, with its halo, in LDS (steps 1 .. 16). variant 0 takes the one
+ * measured faster at each step, 1 the direct one everywhere, 2 the staged one
+ * wherever it fits; the results do not depend on it.
+ * Parity: the arithmetic is csrc/denoise_common.hpp's on both sides and this part of the library is
+ * built like mrt_path_extend's, so imageOut and pixels equal mrth_denoise_filter's (mrt_host.h) bit
+ * for bit; only the bits of a NaN that an operation makes differ.
+ * Checks, in this order, nothing written where one fails: NULL params; width or height < 1, a
+ * negative iterations or normalSquarings, a variant outside 0..2, or a sigmaColor or sigmaPlane that
+ * is not above 0 (a NaN included) is MRT_ERR_INVALID_ARG; width * height above 2^26, iterations above 8 or normalSquarings
+ * above 10 MRT_ERR_TOO_LARGE; then MRT_ERR_INVALID_ARG for a NULL image, guide, albedo or needed
+ * scratch, for imageOut and pixels both NULL, for an image, guide, albedo, needed scratch or
+ * imageOut that is not 16-byte aligned, or for a needed scratch, imageOut or pixels that overlaps an
+ * input or another of them. */
+typedef struct mrt_denoise_params {
+    int32_t width;
+    int32_t height;
+    int32_t iterations;          /* 0..8 */
+    int32_t normalSquarings;     /* 0..10 */
+    float sigmaColor;            /* in units of the demodulated image */
+    float sigmaPlane;            /* in scene units */
+    int32_t variant;             /* 0: the kernel measured faster at each step; 1: direct loads; 2: LDS tiles */
+    int32_t reserved;            /* 0 */
+    const float* image;          /* mrt_path_resolve's float image */
+    const void* guide;           /* mrt_denoise_features' */
+    const float* albedo;
+    float* scratch[2];
+    float* imageOut;             /* may be NULL where pixels is given */
+    uint32_t* pixels;            /* may be NULL where imageOut is given */
+} mrt_denoise_params;
+int  mrt_denoise_filter(const mrt_denoise_params* params, void* stream);
+
 /* ---- a moving scene: normals, colours and the tree's cost on the device ---- */
 /* Scene::Scene's per-triangle tables (reference Scene.cc:37,66-80) from vertices in DEVICE
  * memory: what mrt_raygen_ao / _ao_blocks read as triNormals and mrt_reconstruct as

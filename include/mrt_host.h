@@ -254,6 +254,33 @@ int  mrth_path_accumulate(int32_t numSlots, int32_t numPaths, const void* state,
 int  mrth_path_resolve(int32_t numSamples, int32_t firstPrimary, int32_t numPrimary, const int32_t* primarySlotToId,
                        const void* primaryResults, const float* radiance, uint32_t* pixels, float* image);
 
+/* The CPU statements of mrt_denoise_features and mrt_denoise_filter (mrt.h, which states the
+ * arithmetic and the checks), with the same arguments over HOST memory and no stream, built from
+ * the same header (csrc/denoise_common.hpp) and the same plan: the same bits in every output. The
+ * struct is mrt_denoise_params, field for field. Where mrt.h says MRT_ERR_INVALID_ARG or
+ * MRT_ERR_TOO_LARGE these return MRTH_ERR_INVALID_ARG; alignment and overlap, which matter to the
+ * device's 16-byte accesses and parallel lanes only, are not checked here. */
+int  mrth_denoise_features(int32_t numPrimary, const int32_t* primarySlotToId, const void* primaryRays,
+                           const void* primaryResults, const float* triNormals, const uint32_t* triMaterialColor,
+                           int64_t numTris, int32_t numPixels, void* guide, float* albedo);
+typedef struct mrth_denoise_params {
+    int32_t width;
+    int32_t height;
+    int32_t iterations;
+    int32_t normalSquarings;
+    float sigmaColor;
+    float sigmaPlane;
+    int32_t variant;             /* checked, otherwise ignored: the host has one statement */
+    int32_t reserved;
+    const float* image;
+    const void* guide;
+    const float* albedo;
+    float* scratch[2];
+    float* imageOut;
+    uint32_t* pixels;
+} mrth_denoise_params;
+int  mrth_denoise_filter(const mrth_denoise_params* params);
+
 /* RayBuffer::mortonSort (RayBuffer.cc:256-324): the CPU statement of mrt_ray_sort (mrt.h, which
  * states the key and the order), with the same arguments over HOST memory and no stream. outBox
  * is six host floats (lo.xyz, hi.xyz). The box and the keys are csrc/raysort_common.hpp's on both

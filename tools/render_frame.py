@@ -20,7 +20,10 @@ half-side r, as the reference's shadow generator samples it); without --light th
 carries every primary hit through up to --depth diffuse bounces with a sample of that light at every
 vertex (--light-color r g b) and --sky r g b for the paths that leave the scene; --compact / --in-place
 choose whether live paths are compacted between vertices (default: the Renderer's). Its rate counts
-the paths started, over the summed time of all its traces.
+the paths started, over the summed time of all its traces. --denoise filters a path frame with
+the edge-avoiding wavelet denoiser (Renderer.denoise; --denoise-iterations, --sigma-color,
+--sigma-plane: default a fraction of the scene box's diagonal) before it is written; without it the
+file is what it always was.
 """
 from __future__ import annotations
 
@@ -60,10 +63,16 @@ def main() -> int:
     mode.add_argument("--compact", dest="compact", action="store_true", default=None,
                       help="path: compact the live paths between vertices")
     mode.add_argument("--in-place", dest="compact", action="store_false", help="path: keep every path at its slot")
+    ap.add_argument("--denoise", action="store_true", help="path: filter the frame (Renderer.denoise) before writing it")
+    ap.add_argument("--denoise-iterations", type=int, default=None, help="path, --denoise: a-trous iterations (0..8)")
+    ap.add_argument("--sigma-color", type=float, default=None, help="path, --denoise: colour sigma of the demodulated image")
+    ap.add_argument("--sigma-plane", type=float, default=None, help="path, --denoise: plane-distance sigma in scene units")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--out", default="gpurun_out/frame.ppm")
     a = ap.parse_args()
+    if a.denoise and a.ray_type != "path":
+        ap.error("--denoise filters a --ray-type path frame")
     if not torch.cuda.is_available():
         raise SystemExit("render_frame needs a GPU")
     scene = mrt.Scene.from_obj(a.obj) if a.obj else mrt.Scene.synthetic(a.scene, 0, 1)
@@ -87,18 +96,23 @@ def main() -> int:
     r.begin_frame(cam, w, h)
     counted = r.total_num_rays()
     pixels = torch.zeros(w * h, dtype=torch.int32, device="cuda")
+    image = torch.zeros((w * h, 4), dtype=torch.float32, device="cuda") if a.denoise else None
     ms, batches, live = 0.0, 0, None
     while r.next_batch():
         ms += r.trace_batch()
-        r.update_result(pixels)
+        r.update_result(pixels, image=image)
         batches += 1
         live = list(r.path_stats) if rt == RAY_PATH else None
+    if a.denoise:
+        settings = {k: v for k, v in (("iterations", a.denoise_iterations), ("sigma_color", a.sigma_color)) if v is not None}
+        r.denoise(image, pixels=pixels, sigma_plane=a.sigma_plane, **settings)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     mrt.write_ppm(a.out, pixels.cpu().numpy(), w, h)
     print(json.dumps({"scene": a.obj or a.scene, "camera": a.camera, "ray_type": a.ray_type, "width": w, "height": h,
                       "samples": r.num_samples, "light": light, "light_radius": light_radius, "batches": batches,
-                      **({"depth": a.depth, "compact": r.compact, "live_last_batch": live} if rt == RAY_PATH else {}), "trace_ms": round(ms, 4), "rays_counted": counted,
+                      **({"depth": a.depth, "compact": r.compact, "live_last_batch": live} if rt == RAY_PATH else {}),
+                      **({"denoised": True} if a.denoise else {}), "trace_ms": round(ms, 4), "rays_counted": counted,
                       "mrays_per_s": round(counted / ms / 1e3, 2) if ms > 0 else None, "image": a.out}))
     return 0
 
