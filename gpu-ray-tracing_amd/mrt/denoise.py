@@ -55,7 +55,8 @@ class Denoiser:
                   w: int, h: int, stream=None) -> None:
         """The features of a w x h frame from its traced primary batch (rays and closest-hit
         results), the pixel of every slot, and the current per-triangle normals (float32 [nt, 3])
-        and ABGR colours (int32 [nt]) on the device. Pixels no slot names are misses."""
+        and ABGR colours (int32 [nt]) on the device. Pixels no slot names are misses. Passing
+        stream= alone is enough: the fill for those pixels runs on that stream."""
         if slot_to_id.numel() != primary.size:
             raise _lib.MrtError("slot_to_id must hold one pixel id per primary ray")
         if normals is None or material is None or normals.numel() != 3 * material.numel():
@@ -77,14 +78,16 @@ class Denoiser:
         """Filter `image` (float32 [w*h, 4], mrt_path_resolve's) into pixels (int32 ABGR bits
         [w*h]) and / or image_out (float32 [w*h, 4]); with neither given, pixels is allocated.
         Returns (pixels, image_out). Neither may be `image` itself. sigma_color is in units of the
-        demodulated image, sigma_plane in scene units (Renderer.denoise derives it from the scene's box)."""
+        demodulated image, sigma_plane in scene units (Renderer.denoise derives it from the scene's box).
+        Passing stream= alone is enough: pixels made here are zeroed on that stream."""
         if not self._have_frame:
             raise _lib.MrtError("Denoiser.run before set_frame")
         n = self.w * self.h
         if image.dtype != torch.float32 or image.numel() != 4 * n or not image.is_contiguous():
             raise _lib.MrtError(f"the image is a contiguous float32 [{n}, 4] tensor")
         if pixels is None and image_out is None:
-            pixels = torch.zeros(n, dtype=torch.int32, device=self.device)
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                pixels = torch.zeros(n, dtype=torch.int32, device=self.device)
         if (pixels is not None and pixels.numel() != n) or (image_out is not None and image_out.numel() != 4 * n):
             raise _lib.MrtError("pixels and image_out hold one entry per pixel of the frame")
         p = _lib.DenoiseParams()

@@ -288,18 +288,23 @@ def trace_shard(tracer, rays, world: int, rank: int, max_rays: int = 1 << 21, ex
     RayBuffer first; returns that buffer (its results are the shard's, in
     shard_spans order — what gather_results(..., block=block, owners=owners)
     expects). owners: balance_blocks' deal of the blocks, or None (cyclic);
-    priority: the order of the blocks within the shard (shard_spans)."""
+    priority: the order of the blocks within the shard (shard_spans). Passing stream= alone is
+    enough: the gather of a block-cyclic shard runs on `stream` too (which first waits for
+    torch's current stream, where the rays may have been made)."""
     if block <= 0 or (world == 1 and priority is None):
         lo, hi = shard_range(rays.size, world, rank)
         for a, b in shard_launches(lo, hi, max_rays):
             tracer.trace_async(rays.view(a, b), exact_rcp=exact_rcp, stream=stream)
         return lo, hi
-    from .tracer import RayBuffer
-    local = RayBuffer(local_rays(rays.rays, shard_spans(rays.size, world, rank, block, owners, priority)),
-                      rays.need_closest_hit, secondary=getattr(rays, "secondary", False))
+    from .tracer import RayBuffer, _on_stream
     if stream is not None:
-        # the local buffer was built on the current stream: the launches on `stream` wait for it
+        # rays made on the current stream, as before: `stream` waits for them
         stream.wait_stream(torch.cuda.current_stream())
+    with _on_stream(stream):
+        # the local buffer is gathered on `stream`, after what the caller enqueued there as well,
+        # and the launches follow it: passing stream= alone is enough
+        local = RayBuffer(local_rays(rays.rays, shard_spans(rays.size, world, rank, block, owners, priority)),
+                          rays.need_closest_hit, secondary=getattr(rays, "secondary", False))
     for a, b in shard_launches(0, local.size, max_rays):
         tracer.trace_async(local.view(a, b), exact_rcp=exact_rcp, stream=stream)
     return local

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .host import path_params
-from .tracer import RayBuffer, Tracer, _stream_ptr
+from .tracer import RayBuffer, Tracer, _on_stream, _stream_ptr
 
 MAX_PATHS = _lib.MRT_PATH_MAX_PATHS
 MAX_DEPTH = _lib.MRT_PATH_MAX_DEPTH
@@ -80,7 +80,8 @@ class PathIntegrator:
     def extend_async(self, vertex: int, stream=None) -> None:
         """The vertex step over the current slots, enqueued with no host sync. The bounce rays and
         states land in the other half of the ping-pong pair, which trace_bounce makes the current
-        one; the live count lands in self.live_count (device int32)."""
+        one; the live count lands in self.live_count (device int32). Every launch goes to `stream`
+        and nothing is allocated here, so passing stream= alone is enough."""
         n, cur, nxt = self.num_slots, self._cur, 1 - self._cur
         p = path_params(vertex, **self._scalars)
         p.triNormals, p.triMaterialColor, p.numTris = self.normals.data_ptr(), self.material.data_ptr(), self.material.numel()
@@ -100,9 +101,11 @@ class PathIntegrator:
 
     def extend(self, vertex: int, stream=None) -> int:
         """extend_async, then one blocking 4-byte readback of the live count, which it returns: a
-        trace takes its ray count on the host."""
+        trace takes its ray count on the host. The readback runs ON `stream`, after the step, so
+        passing stream= alone is enough, whatever torch's current stream is."""
         self.extend_async(vertex, stream)
-        self.live = int(self.live_count.item()) if self.num_slots else 0
+        with _on_stream(stream):
+            self.live = int(self.live_count.item()) if self.num_slots else 0
         self.stats.append(self.live)
         if self.compact:
             self.num_slots = self.live
@@ -122,6 +125,8 @@ class PathIntegrator:
         return self.tracer.trace_batch(self.shadow_batch(), exact_rcp=exact_rcp) if self.num_slots else 0.0
 
     def accumulate(self, stream=None) -> None:
+        """radiance += pending where the slot's shadow ray reached the light (mrt_path_accumulate),
+        enqueued on `stream` with no host sync; nothing is allocated, so stream= alone is enough."""
         m, nxt = self.num_slots, 1 - self._cur
         _lib.check(self.lib.mrt_path_accumulate(m, self.num_paths, self.state[nxt].data_ptr(), self.pending.data_ptr(),
                                                 self.shadow_results.data_ptr(), self.radiance.data_ptr(),
@@ -149,11 +154,13 @@ class PathIntegrator:
     def resolve(self, slot_to_id: torch.Tensor, num_pixels: int, pixels: torch.Tensor | None = None,
                 image: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         """The batch's pixels (int32 ABGR bits) at slot_to_id[first + i]; image (float32
-        [num_pixels, 4], optional) gets the unclamped values."""
+        [num_pixels, 4], optional) gets the unclamped values. Enqueued on `stream` with no host
+        sync; pixels made here are zeroed on that stream, so passing stream= alone is enough."""
         if slot_to_id.numel() != self.primary.size:
             raise _lib.MrtError("slot_to_id must hold one pixel id per primary ray")
         if pixels is None:
-            pixels = torch.zeros(num_pixels, dtype=torch.int32, device=self.device)
+            with _on_stream(stream):
+                pixels = torch.zeros(num_pixels, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.mrt_path_resolve(self.num_samples, self.first, self.count, slot_to_id.data_ptr(),
                                              self.primary.results.data_ptr(), self.radiance.data_ptr(),
                                              pixels.data_ptr(), None if image is None else image.data_ptr(),

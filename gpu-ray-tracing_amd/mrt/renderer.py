@@ -38,7 +38,7 @@ from .denoise import SIGMA_PLANE_FRACTION_DEFAULT, Denoiser
 from .host import Camera, Scene
 from .path import PathIntegrator
 from .raygen import RAY_AO, RAY_DIFFUSE, RAY_PATH, RAY_PRIMARY, RAY_SHADOW, DeviceRayGen, DeviceReconstructor
-from .tracer import RayBuffer, Tracer
+from .tracer import RayBuffer, Tracer, _on_stream
 
 MAX_BATCH_RAYS = 1 << 21   # Renderer.cc:46 m_raygen(1 << 21)
 # Whether a RAY_PATH frame compacts its live paths between vertices unless set_params says
@@ -153,7 +153,8 @@ class Renderer:
         is uploaded): the tracer's bound tree is refitted (Tracer.refit) and the normals and
         colours the frame path reads are recomputed on the device (set_geometry of the ray
         generator and the reconstructor), all on `stream`, nothing crossing to the host. Frames
-        begun afterwards on that stream see the moved scene.
+        begun afterwards on that stream see the moved scene. Passing stream= alone is enough: the
+        uploads and conversions made here are ordered on that stream too.
         rebuild_above=r: the refitted tree's SAH cost is then read (Tracer.tree_cost: one blocking
         64-byte readback) and, where it exceeds r times the baseline, the tree is rebuilt from the
         moved vertices (Tracer.build(..., on_device=True); the renderer keeps the GpuBvh alive) and
@@ -166,16 +167,17 @@ class Renderer:
         if self.tracer.bvh is None:
             raise _lib.MrtError("Renderer.set_vertices: the tracer has no BVH")
         dev = self.gen.device
-        if self._triangles is None:
-            _, tris, _ = self.scene.arrays()
-            self._triangles = torch.from_numpy(tris).to(dev)
-            self._diffuse = torch.from_numpy(self.scene.tri_diffuse()).to(dev)
-        if self._recon is None:
-            self._recon = DeviceReconstructor(self.scene)
-        if isinstance(vertices, torch.Tensor):
-            v = vertices.to(dev, torch.float32).contiguous().view(-1, 3)
-        else:
-            v = torch.from_numpy(np.array(vertices, np.float32).reshape(-1, 3)).to(dev)
+        with _on_stream(stream):   # uploads and conversions go to the stream the launches run on
+            if self._triangles is None:
+                _, tris, _ = self.scene.arrays()
+                self._triangles = torch.from_numpy(tris).to(dev)
+                self._diffuse = torch.from_numpy(self.scene.tri_diffuse()).to(dev)
+            if self._recon is None:
+                self._recon = DeviceReconstructor(self.scene)
+            if isinstance(vertices, torch.Tensor):
+                v = vertices.to(dev, torch.float32).contiguous().view(-1, 3)
+            else:
+                v = torch.from_numpy(np.array(vertices, np.float32).reshape(-1, 3)).to(dev)
         if rebuild_above is not None and self._baseline_of is not self.tracer.bvh:
             self._baseline_sah, self._baseline_of = self.tracer.tree_cost(stream)["sah"], self.tracer.bvh
         self.tracer.refit(v, self._triangles, stream=stream)

@@ -10,6 +10,7 @@ Tracer constructor raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -23,6 +24,14 @@ def _stream_ptr(stream) -> int | None:
     if stream is None:
         stream = torch.cuda.current_stream()
     return stream.cuda_stream or None
+
+
+def _on_stream(stream):
+    """`stream` as torch's current stream for the length of a `with` block (nothing where stream is
+    None: the current stream stays). Every method that takes stream= runs under it, so that what
+    it allocates, fills, uploads and reads back is ordered on the stream its launches go to:
+    passing stream= alone is enough, whatever torch's current stream is."""
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
 
 class GpuBvh:
@@ -99,7 +108,9 @@ class RayBuffer:
         (None = the identity). Returns (sorted RayBuffer, id_to_slot, slot_to_id) — id_to_slot
         starts at -1 and is what reconstruct takes as batch_id_to_slot — and, with want_keys,
         also keys (uint32 bits as int32 [n, 6], in this buffer's order) and box (float32 [6]).
-        The new buffer keeps need_closest_hit and secondary and has fresh results."""
+        The new buffer keeps need_closest_hit and secondary and has fresh results. Passing stream=
+        alone is enough: the tensors returned are allocated, and id_to_slot and the new results
+        filled, on that stream."""
         dev = self.rays.device
         n = self.size
         if dev.type != "cuda":
@@ -107,18 +118,19 @@ class RayBuffer:
         if slot_to_id is not None and (slot_to_id.dtype != torch.int32 or tuple(slot_to_id.shape) != (n,) or
                                        slot_to_id.device != dev or not slot_to_id.is_contiguous()):
             raise _lib.MrtError("morton_sort: slot_to_id must be a contiguous int32 [n] tensor on the rays' device")
-        out = torch.empty_like(self.rays)
-        id_to_slot = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        new_slot_to_id = torch.empty(n, dtype=torch.int32, device=dev)
-        keys = torch.empty((n, 6), dtype=torch.int32, device=dev) if want_keys else None
-        box_out = torch.empty(6, dtype=torch.float32, device=dev) if want_keys else None
-        params = _lib.RaySortParams(drop_levels=int(drop_levels), box=int(box))
-        _lib.check(_lib.trace_lib().mrt_ray_sort(
-            self.rays.data_ptr(), None if slot_to_id is None else slot_to_id.data_ptr(), n, C.byref(params),
-            out.data_ptr(), id_to_slot.data_ptr(), new_slot_to_id.data_ptr(),
-            None if keys is None else keys.data_ptr(), None if box_out is None else box_out.data_ptr(),
-            _stream_ptr(stream)))
-        rb = RayBuffer(out, self.need_closest_hit, dev, secondary=self.secondary)
+        with _on_stream(stream):
+            out = torch.empty_like(self.rays)
+            id_to_slot = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            new_slot_to_id = torch.empty(n, dtype=torch.int32, device=dev)
+            keys = torch.empty((n, 6), dtype=torch.int32, device=dev) if want_keys else None
+            box_out = torch.empty(6, dtype=torch.float32, device=dev) if want_keys else None
+            params = _lib.RaySortParams(drop_levels=int(drop_levels), box=int(box))
+            _lib.check(_lib.trace_lib().mrt_ray_sort(
+                self.rays.data_ptr(), None if slot_to_id is None else slot_to_id.data_ptr(), n, C.byref(params),
+                out.data_ptr(), id_to_slot.data_ptr(), new_slot_to_id.data_ptr(),
+                None if keys is None else keys.data_ptr(), None if box_out is None else box_out.data_ptr(),
+                _stream_ptr(stream)))
+            rb = RayBuffer(out, self.need_closest_hit, dev, secondary=self.secondary)
         if want_keys:
             return rb, id_to_slot, new_slot_to_id, keys, box_out
         return rb, id_to_slot, new_slot_to_id
@@ -265,7 +277,8 @@ class Tracer:
         """Refit the bound BVH in place for moved vertices (mrt_tracer_refit): stream-ordered,
         no host sync after the first call. vertices float32 [nv, 3], triangles int32 [nt, 3]
         (the triangles the BVH was built over) as device tensors; numpy arrays are uploaded.
-        Writes the bound GpuBvh's nodes and woop tensors."""
+        Writes the bound GpuBvh's nodes and woop tensors. Passing stream= alone is enough: an upload
+        or a conversion of the arguments is ordered on that stream too."""
         if self.bvh is None:
             raise _lib.MrtError("Tracer: No BVH!")
         dev = self.bvh.device
@@ -275,10 +288,11 @@ class Tracer:
                 return a.to(dev, dtype).contiguous().view(-1, 3)
             a = np.ascontiguousarray(a, np_dtype).reshape(-1, 3)
             return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-        v = on_device(vertices, torch.float32, np.float32)
-        t = on_device(triangles, torch.int32, np.int32)
-        _lib.check(self.lib.mrt_tracer_refit(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0],
-                                             _stream_ptr(stream)))
+        with _on_stream(stream):
+            v = on_device(vertices, torch.float32, np.float32)
+            t = on_device(triangles, torch.int32, np.int32)
+            _lib.check(self.lib.mrt_tracer_refit(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0],
+                                                 _stream_ptr(stream)))
         self._refit_inputs = (v, t)   # the launches may still read them
 
     def refit_info(self) -> dict:
@@ -294,15 +308,17 @@ class Tracer:
         sah = (Cn * inner_area + Ct * leaf_tri_area) / root_area (mrt.host.tree_cost_dict). Ordered
         after a refit on `stream`. sync=True blocks for one 64-byte readback and returns the dict;
         sync=False enqueues only and returns an 8-word float64 device tensor holding the
-        mrt_tree_cost bytes (mrt.tracer.tree_cost_from_tensor reads it after a sync)."""
+        mrt_tree_cost bytes (mrt.tracer.tree_cost_from_tensor reads it after a sync), allocated on
+        `stream`: passing stream= alone is enough in both forms."""
         if self.bvh is None:
             raise _lib.MrtError("Tracer: No BVH!")
         if sync:
             c = _lib.TreeCost()
             _lib.check(self.lib.mrt_tracer_tree_cost(self._h, C.byref(c), None, _stream_ptr(stream)))
             return tree_cost_dict(c)
-        out = torch.empty(8, dtype=torch.float64, device=self.bvh.device)
-        _lib.check(self.lib.mrt_tracer_tree_cost(self._h, None, out.data_ptr(), _stream_ptr(stream)))
+        with _on_stream(stream):
+            out = torch.empty(8, dtype=torch.float64, device=self.bvh.device)
+            _lib.check(self.lib.mrt_tracer_tree_cost(self._h, None, out.data_ptr(), _stream_ptr(stream)))
         return out
 
     # -- re-optimise (treelet restructuring) ---------------------------------------
@@ -333,7 +349,8 @@ class Tracer:
         Faster than mrt.Bvh.build + upload by orders of magnitude, slower to trace (no SAH, no
         spatial splits): for new or re-meshed geometry; Tracer.refit covers moved vertices.
         on_device: the level plan and the bind's 4-wide array are derived on the device too
-        (mrt_tracer_build_device: the same bytes, no node array crosses to the host)."""
+        (mrt_tracer_build_device: the same bytes, no node array crosses to the host).
+        Passing stream= alone is enough: the uploads and the tree's tensors are ordered on it."""
         dev = torch.device("cuda", self.device)
 
         def to_device(a, dtype, np_dtype):
@@ -341,18 +358,19 @@ class Tracer:
                 return a.to(dev, dtype).contiguous().view(-1, 3)
             a = np.ascontiguousarray(a, np_dtype).reshape(-1, 3)
             return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-        v = to_device(vertices, torch.float32, np.float32)
-        t = to_device(triangles, torch.int32, np.int32)
-        cap = [C.c_int64(), C.c_int64(), C.c_int64()]
-        _lib.check(self.lib.mrt_lbvh_sizes(t.shape[0], *map(C.byref, cap)))
-        nodes, woop, tri = (torch.empty(c.value // 4, dtype=torch.int32, device=dev) for c in cap)
-        params = _lib.LbvhParams(max_leaf_size=int(max_leaf_size or 0))
-        out = [C.c_int64(), C.c_int64(), C.c_int64()]
-        fn = self.lib.mrt_tracer_build_device if on_device else self.lib.mrt_tracer_build
-        _lib.check(fn(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0],
-                      C.byref(params), nodes.data_ptr(), cap[0].value, woop.data_ptr(),
-                      cap[1].value, tri.data_ptr(), cap[2].value, *map(C.byref, out),
-                      _stream_ptr(stream)))
+        with _on_stream(stream):
+            v = to_device(vertices, torch.float32, np.float32)
+            t = to_device(triangles, torch.int32, np.int32)
+            cap = [C.c_int64(), C.c_int64(), C.c_int64()]
+            _lib.check(self.lib.mrt_lbvh_sizes(t.shape[0], *map(C.byref, cap)))
+            nodes, woop, tri = (torch.empty(c.value // 4, dtype=torch.int32, device=dev) for c in cap)
+            params = _lib.LbvhParams(max_leaf_size=int(max_leaf_size or 0))
+            out = [C.c_int64(), C.c_int64(), C.c_int64()]
+            fn = self.lib.mrt_tracer_build_device if on_device else self.lib.mrt_tracer_build
+            _lib.check(fn(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0],
+                          C.byref(params), nodes.data_ptr(), cap[0].value, woop.data_ptr(),
+                          cap[1].value, tri.data_ptr(), cap[2].value, *map(C.byref, out),
+                          _stream_ptr(stream)))
         bvh = GpuBvh.__new__(GpuBvh)
         bvh.nodes, bvh.woop, bvh.tri_index = (a[:o.value // 4] for a, o in zip((nodes, woop, tri), out))
         bvh.device = dev
@@ -388,14 +406,16 @@ class Tracer:
         return f
 
     def trace_async(self, rays: RayBuffer, exact_rcp=False, speculative=True, stats=False, stream=None) -> None:
-        """Stream-ordered trace of the whole batch (no host sync)."""
+        """Stream-ordered trace of the whole batch (no host sync). Passing stream= alone is enough:
+        a stats tensor it makes is zeroed on that stream."""
         if self.bvh is None:
             raise _lib.MrtError("Tracer: No BVH!")   # CudaTracer.cc:129-130
         f = self.flags(rays, exact_rcp, speculative, stats)
         sp = None
         if stats:
             if rays.stats is None or rays.stats.shape[0] != rays.size:
-                rays.stats = torch.zeros((rays.size, 4), dtype=torch.int32, device=rays.rays.device)
+                with _on_stream(stream):
+                    rays.stats = torch.zeros((rays.size, 4), dtype=torch.int32, device=rays.rays.device)
             sp = rays.stats.data_ptr()
         _lib.check(self.lib.mrt_tracer_trace(self._h, rays.rays.data_ptr(), rays.results.data_ptr(), rays.size, f,
                                              sp, _stream_ptr(stream)))
@@ -418,14 +438,16 @@ class Tracer:
         return launch
 
     def trace_batch(self, rays: RayBuffer, exact_rcp=False, speculative=True, stats=False, stream=None) -> float:
-        """CudaTracer::traceBatch: blocking, returns the launch's milliseconds (0 for no rays)."""
+        """CudaTracer::traceBatch: blocking, returns the launch's milliseconds (0 for no rays). The
+        launch runs on `stream`, and so does the zeroing of a stats tensor it makes."""
         if self.bvh is None:
             raise _lib.MrtError("Tracer: No BVH!")
         f = self.flags(rays, exact_rcp, speculative, stats)
         sp = None
         if stats:
             if rays.stats is None or rays.stats.shape[0] != rays.size:
-                rays.stats = torch.zeros((rays.size, 4), dtype=torch.int32, device=rays.rays.device)
+                with _on_stream(stream):
+                    rays.stats = torch.zeros((rays.size, 4), dtype=torch.int32, device=rays.rays.device)
             sp = rays.stats.data_ptr()
         info = _lib.TraceInfo()
         _lib.check(self.lib.mrt_tracer_trace_timed(self._h, rays.rays.data_ptr(), rays.results.data_ptr(), rays.size,
