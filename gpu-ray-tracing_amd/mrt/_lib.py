@@ -1,6 +1,7 @@
 """ctypes bindings of the two in-tree native libraries.
 
 lib/libmrt.so       include/mrt.h       (gfx950 traversal kernels + C-ABI; the hot path)
+                    include/mrt_temporal.h  (the temporal accumulation's two exports)
 lib/libmrt_host.so  include/mrt_host.h  (scenes, SBVH builder, Compact2, ray generation)
 
 Both are built by ``make -C gpu-ray-tracing_amd`` (``__graft_entry__.build()``).
@@ -117,11 +118,22 @@ class DenoiseParams(C.Structure):
                 ("pixels", vp)]
 
 
+class TemporalParams(C.Structure):
+    """mrt_temporal_params / mrth_temporal_params (one layout)."""
+    _fields_ = [("width", i32), ("height", i32), ("havePrev", i32), ("maxHistory", i32), ("normalCos", f32),
+                ("sigmaPlane", f32), ("variant", i32), ("reserved", i32), ("prevWorldToScreen", f32 * 16),
+                ("prevSubpixel", f32 * 2), ("image", vp), ("guide", vp), ("albedo", vp), ("prevPosition", vp),
+                ("prevGuide", vp), ("prevHistory", vp), ("history", vp), ("imageOut", vp), ("pixels", vp)]
+
+
 MRT_DENOISE_MAX_PIXELS = 1 << 26    # csrc/denoise_limits.hpp
 MRT_DENOISE_MAX_ITERATIONS = 8
 MRT_DENOISE_MAX_SQUARINGS = 10
 MRT_DENOISE_TILE = (32, 8)          # the direct filter workgroup's pixels: width, height
 MRT_DENOISE_ROW_TILE = (64, 4)      # the LDS-staged one's: columns, rows a step apart
+MRT_TEMPORAL_MAX_PIXELS = 1 << 26   # csrc/temporal_limits.hpp
+MRT_TEMPORAL_MAX_HISTORY = 1 << 20
+MRT_TEMPORAL_TILE = (32, 8)         # the tiled accumulate workgroup's pixels: width, height
 MRT_PATH_MAX_PATHS = 1 << 22    # csrc/path_limits.hpp
 MRT_PATH_MAX_DEPTH = 64
 MRT_PATH_SCAN_ROUND_SLOTS = 1024 * 256   # slots whose workgroup counts fill one round of the scan
@@ -247,6 +259,12 @@ TRACE_SYMBOLS = [
     ("launch_reorderRaysKernel", None, [i32, C.POINTER(ReorderRaysInput)]),
 ]
 
+# (name, restype, argtypes) of every symbol include/mrt_temporal.h declares (libmrt.so's too).
+TEMPORAL_SYMBOLS = [
+    ("mrt_temporal_motion", i32, [i32, vp, vp, vp, vp, i64, vp, vp, i64, i32, vp, vp]),
+    ("mrt_temporal_accumulate", i32, [C.POINTER(TemporalParams), vp]),
+]
+
 # (name, restype, argtypes) of every symbol include/mrt_host.h declares.
 HOST_SYMBOLS = [
     ("mrth_scene_synthetic", i32, [C.c_char_p, i64, C.c_uint64, C.POINTER(vp)]),
@@ -291,6 +309,8 @@ HOST_SYMBOLS = [
     ("mrth_path_resolve", i32, [i32, i32, i32, vp, vp, vp, vp, vp]),
     ("mrth_denoise_features", i32, [i32, vp, vp, vp, vp, vp, i64, i32, vp, vp]),
     ("mrth_denoise_filter", i32, [C.POINTER(DenoiseParams)]),
+    ("mrth_temporal_motion", i32, [i32, vp, vp, vp, vp, i64, vp, vp, i64, i32, vp]),
+    ("mrth_temporal_accumulate", i32, [C.POINTER(TemporalParams)]),
     ("mrth_ray_sort", i32, [vp, vp, i32, C.POINTER(RaySortParams), vp, vp, vp, vp, vp]),
     ("mrth_last_error", C.c_char_p, []),
 ]
@@ -314,7 +334,7 @@ def _load(path: str, symbols):
 def trace_lib():
     global _trace_lib
     if _trace_lib is None:
-        _trace_lib = _load(TRACE_LIB_PATH, TRACE_SYMBOLS)
+        _trace_lib = _load(TRACE_LIB_PATH, TRACE_SYMBOLS + TEMPORAL_SYMBOLS)
     return _trace_lib
 
 

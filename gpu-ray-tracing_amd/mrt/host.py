@@ -542,6 +542,67 @@ def denoise_filter(image, guide, albedo, width: int, height: int, iterations: in
     return out, pixels
 
 
+def temporal_motion(slot_to_id, primary_rays, primary_results, triangles, vertices, prev_vertices, num_pixels: int,
+                    prev_position: np.ndarray | None = None):
+    """mrth_temporal_motion (the CPU statement of mrt_temporal_motion, whose bits it gives): where
+    every primary hit's surface point was in the previous frame (float32 [num_pixels, 4]: the
+    position and 1, zeros at a miss), at slot_to_id's pixels. Pixels no slot names keep what
+    `prev_position` held (zeros where none is passed)."""
+    s2i = np.ascontiguousarray(slot_to_id, np.int32).reshape(-1)
+    r = np.ascontiguousarray(primary_rays, np.float32).reshape(-1, 8)
+    res = np.ascontiguousarray(primary_results).view(np.int32).reshape(-1, 4)
+    tri = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    pv = np.ascontiguousarray(prev_vertices, np.float32).reshape(-1, 3)
+    if len(r) != len(s2i) or len(res) != len(s2i) or len(v) != len(pv):
+        raise _lib.MrtError("temporal_motion: one ray and one result per slot, one previous vertex per vertex")
+    if prev_position is None:
+        prev_position = np.zeros((num_pixels, 4), np.float32)
+    if prev_position.dtype != np.float32 or prev_position.shape != (num_pixels, 4) or not prev_position.flags.c_contiguous:
+        raise _lib.MrtError(f"temporal_motion: prev_position is a contiguous float32 [{num_pixels}, 4] array")
+    _lib.check_host(_lib.host_lib().mrth_temporal_motion(len(s2i), _ptr(s2i), _ptr(r), _ptr(res), _ptr(tri) if len(tri) else None,
+                                                         len(tri), _ptr(v) if len(v) else None, _ptr(pv) if len(v) else None,
+                                                         len(v), num_pixels, _ptr(prev_position)))
+    return prev_position
+
+
+def temporal_accumulate(image, guide, albedo, width: int, height: int, prev_guide=None, prev_history=None,
+                        prev_world_to_screen=None, prev_subpixel=(0.5, 0.5), prev_position=None, max_history: int = 32,
+                        normal_cos: float = 0.8, sigma_plane: float = 1.0, want_image: bool = True,
+                        want_pixels: bool = True, have_prev: bool | None = None):
+    """mrth_temporal_accumulate (the CPU statement of mrt_temporal_accumulate, whose bits it gives):
+    one frame of the running mean over a width x height float image. have_prev None: whether
+    prev_guide and prev_history are given. Returns (history float32 [w*h, 4], image_out float32
+    [w*h, 4] or None, pixels uint32 [w*h] or None)."""
+    n = int(width) * int(height)
+    img = np.ascontiguousarray(image, np.float32).reshape(-1, 4)
+    gd = np.ascontiguousarray(guide, np.float32).reshape(-1, 8)
+    alb = np.ascontiguousarray(albedo, np.float32).reshape(-1, 4)
+    pg = None if prev_guide is None else np.ascontiguousarray(prev_guide, np.float32).reshape(-1, 8)
+    ph = None if prev_history is None else np.ascontiguousarray(prev_history, np.float32).reshape(-1, 4)
+    pp = None if prev_position is None else np.ascontiguousarray(prev_position, np.float32).reshape(-1, 4)
+    if width < 1 or height < 1 or any(a is not None and len(a) != n for a in (img, gd, alb, pg, ph, pp)):
+        raise _lib.MrtError("temporal_accumulate: every buffer holds one entry per pixel of the frame")
+    p = _lib.TemporalParams()
+    p.width, p.height, p.maxHistory = int(width), int(height), int(max_history)
+    p.havePrev = int(pg is not None and ph is not None) if have_prev is None else int(bool(have_prev))
+    p.normalCos, p.sigmaPlane = float(np.float32(normal_cos)), float(np.float32(sigma_plane))
+    m = np.zeros(16, np.float32) if prev_world_to_screen is None else np.asarray(prev_world_to_screen, np.float32).reshape(16)
+    for i in range(16):
+        p.prevWorldToScreen[i] = float(m[i])
+    p.prevSubpixel[0], p.prevSubpixel[1] = float(np.float32(prev_subpixel[0])), float(np.float32(prev_subpixel[1]))
+    history = np.zeros((n, 4), np.float32)
+    out = np.zeros((n, 4), np.float32) if want_image else None
+    pixels = np.zeros(n, np.uint32) if want_pixels else None
+    p.image, p.guide, p.albedo = _ptr(img), _ptr(gd), _ptr(alb)
+    p.prevPosition = None if pp is None else _ptr(pp)
+    p.prevGuide, p.prevHistory = (None if pg is None else _ptr(pg)), (None if ph is None else _ptr(ph))
+    p.history = _ptr(history)
+    p.imageOut, p.pixels = (None if out is None else _ptr(out)), (None if pixels is None else _ptr(pixels))
+    _lib.check_host(_lib.host_lib().mrth_temporal_accumulate(C.byref(p)))
+    return history, out, pixels
+
+
 def ray_sort(rays, slot_to_id=None, drop_levels: int = 0, box: int = 0) -> dict:
     """RayBuffer::mortonSort on the host (mrth_ray_sort; the CPU statement of
     RayBuffer.morton_sort, whose bits it reproduces): the batch in the order of the reference's

@@ -20,7 +20,8 @@ light, batched and seeded like AO, reconstructed by DeviceReconstructor.reconstr
 
 A fifth, RAY_PATH, carries the same batches of primary hits through up to `depth` diffuse bounces
 with a light sample at every vertex (mrt.path.PathIntegrator): next_batch starts a
-batch's paths, trace_batch runs its vertices, update_result resolves it.
+batch's paths, trace_batch runs its vertices, update_result resolves it. accumulate blends the
+resolved frame into the history of the frames before it (mrt.temporal), denoise filters it.
 
 The reference draws every AO/diffuse batch seed from the C library's rand()
 (RayGen.cc:106; App never seeds it, so the sequence starts at glibc's
@@ -37,6 +38,7 @@ from . import _lib
 from .denoise import SIGMA_PLANE_FRACTION_DEFAULT, Denoiser
 from .host import Camera, Scene
 from .path import PathIntegrator
+from . import temporal as _temporal
 from .raygen import RAY_AO, RAY_DIFFUSE, RAY_PATH, RAY_PRIMARY, RAY_SHADOW, DeviceRayGen, DeviceReconstructor
 from .tracer import RayBuffer, Tracer, _on_stream
 
@@ -106,7 +108,15 @@ class Renderer:
         self._paths: PathIntegrator | None = None
         self.path_stats: list[int] = []   # the last path batch's live counts per vertex
         self._denoiser: Denoiser | None = None   # made by the first denoise()
-        self._diagonal: float | None = None      # of the scene's box, for denoise's default sigma_plane
+        self._diagonal: float | None = None      # of the scene's box, for the default sigma_plane of denoise and accumulate
+        # accumulate: made by the first call; from then on set_vertices keeps the vertices of its
+        # last call (_vertices) and those the last accumulated frame saw (_motion_from, until the
+        # next accumulate has reprojected through them)
+        self._temporal: _temporal.TemporalAccumulator | None = None
+        self._vertices = self._motion_from = None
+        self._moved_unseen = False    # a set_vertices before the first accumulate: its vertices were not kept
+        self._temporal_tris = -1      # the triangle count the history was accumulated over
+        self._subpixel = (0.5, 0.5)
         self.primary: RayBuffer | None = None
         self.slot_to_id: torch.Tensor | None = None
         self.batch: RayBuffer | None = None
@@ -178,6 +188,10 @@ class Renderer:
                 v = vertices.to(dev, torch.float32).contiguous().view(-1, 3)
             else:
                 v = torch.from_numpy(np.array(vertices, np.float32).reshape(-1, 3)).to(dev)
+            if self._temporal is not None:   # the previous frame's vertices, for accumulate's reprojection
+                self._keep_motion(v, dev)
+            else:
+                self._moved_unseen = True
         if rebuild_above is not None and self._baseline_of is not self.tracer.bvh:
             self._baseline_sah, self._baseline_of = self.tracer.tree_cost(stream)["sah"], self.tracer.bvh
         self.tracer.refit(v, self._triangles, stream=stream)
@@ -195,8 +209,25 @@ class Renderer:
             out["rebuilt"] = True
         return out
 
+    def _keep_motion(self, v: torch.Tensor, dev) -> None:
+        """set_vertices after the first accumulate(): a device clone of v (made on the stream
+        set_vertices runs on) becomes the current vertices; the ones before it, those the last
+        accumulated frame saw, are kept until the next accumulate. Before any set_vertices they are
+        the scene's vertices as loaded. Vertices that an earlier set_vertices brought and nobody
+        kept cannot be reprojected from: the history starts over."""
+        if self._vertices is None:
+            if self._moved_unseen:
+                self._temporal.reset()
+            else:
+                self._vertices = torch.from_numpy(self.scene.arrays()[0]).to(dev)
+        if self._motion_from is None:
+            self._motion_from = self._vertices
+        self._vertices = v.clone()
+        self._moved_unseen = False
+
     def begin_frame(self, cam: Camera, w: int, h: int, subpixel=(0.5, 0.5)) -> None:
         self.cam, self.w, self.h = cam, w, h
+        self._subpixel = (float(subpixel[0]), float(subpixel[1]))
         self.primary, self.slot_to_id = self.gen.primary(cam, w, h, subpixel=subpixel)
         if self.ray_type != RAY_PRIMARY:
             self.tracer.trace_batch(self.primary, exact_rcp=self.exact_rcp)
@@ -351,14 +382,53 @@ class Renderer:
         if self._denoiser is None:
             self._denoiser = Denoiser(self.gen.device)
         if sigma_plane is None:
-            if self._diagonal is None:
-                v = self.scene.arrays()[0].astype(np.float64)
-                self._diagonal = float(np.linalg.norm(v.max(axis=0) - v.min(axis=0))) if len(v) else 1.0
-            sigma_plane = max(self._diagonal, 1.0e-30) * SIGMA_PLANE_FRACTION_DEFAULT
+            sigma_plane = self._default_sigma_plane(SIGMA_PLANE_FRACTION_DEFAULT)
         self._denoiser.set_frame(self.primary, self.slot_to_id, self.gen.normals, self._recon.material, self.w, self.h,
                                  stream=stream)
         return self._denoiser.run(image, pixels=pixels, image_out=image_out, sigma_plane=sigma_plane, stream=stream,
                                   **settings)
+
+    def _default_sigma_plane(self, fraction: float) -> float:
+        if self._diagonal is None:
+            v = self.scene.arrays()[0].astype(np.float64)
+            self._diagonal = float(np.linalg.norm(v.max(axis=0) - v.min(axis=0))) if len(v) else 1.0
+        return max(self._diagonal, 1.0e-30) * fraction
+
+    def accumulate(self, image: torch.Tensor, pixels: torch.Tensor | None = None, image_out: torch.Tensor | None = None,
+                   sigma_plane: float | None = None, reset: bool = False, **settings):
+        """Temporal accumulation (mrt.temporal.TemporalAccumulator) of a RAY_PATH frame's
+        float image, called after the frame's last update_result(pixels, image=image) and before
+        denoise, whose input is then image_out: the frame is blended into the running mean of the
+        frames accumulated before it, found where each pixel's surface point was in the previous
+        one, through the camera's motion and, after a set_vertices between the two frames, the
+        triangles' motion. The result goes to pixels (w*h ABGR int32) and / or image_out (float32
+        [w*h, 4], not `image` itself); returns (pixels, image_out). settings:
+        TemporalAccumulator.accumulate's max_history, normal_cos and variant. sigma_plane None:
+        mrt.temporal.SIGMA_PLANE_FRACTION_DEFAULT of the diagonal of the scene's box (of its vertices
+        as loaded). reset=True, another frame size and another triangle count (a Tracer.build in
+        between) start a new history. It takes no stream: it runs on torch's current stream, so to
+        use a side stream s call it under `with torch.cuda.stream(s)`. Nothing waits on the host."""
+        if self.ray_type != RAY_PATH:
+            raise _lib.MrtError("Renderer.accumulate: only a RAY_PATH frame is accumulated")
+        if self.primary is None or self._recon is None:
+            raise _lib.MrtError("Renderer.accumulate before begin_frame and the frame's batches")
+        if self._temporal is None:
+            self._temporal = _temporal.TemporalAccumulator(self.gen.device)
+        material = self._recon.material
+        if reset or material.numel() != self._temporal_tris:
+            self._temporal.reset()
+        if sigma_plane is None:
+            sigma_plane = self._default_sigma_plane(_temporal.SIGMA_PLANE_FRACTION_DEFAULT)
+        prev = self._motion_from
+        if prev is not None and (prev.numel() != self._vertices.numel() or self._triangles.numel() != 3 * material.numel()):
+            prev = None               # another mesh: nothing to reproject through
+            self._temporal.reset()
+        out = self._temporal.accumulate(self.primary, self.slot_to_id, self.gen.normals, material, self.w, self.h,
+                                        _temporal.world_to_screen(self.cam, self.w, self.h), self._subpixel, image,
+                                        pixels=pixels, image_out=image_out, triangles=self._triangles,
+                                        vertices=self._vertices, prev_vertices=prev, sigma_plane=sigma_plane, **settings)
+        self._motion_from, self._temporal_tris = None, material.numel()
+        return out
 
     def batches(self):
         """Every batch of the frame (generated, not traced) as (RayBuffer, first ray) pairs."""

@@ -281,6 +281,40 @@ typedef struct mrth_denoise_params {
 } mrth_denoise_params;
 int  mrth_denoise_filter(const mrth_denoise_params* params);
 
+/* The CPU statements of mrt_temporal_motion and mrt_temporal_accumulate (mrt_temporal.h, which
+ * states the arithmetic and the checks), with the same arguments over HOST memory and no stream,
+ * built from the same header (csrc/temporal_common.hpp) and the same plan: the same bits in every
+ * output. The struct is mrt_temporal_params, field for field. Where mrt_temporal.h says
+ * MRT_ERR_INVALID_ARG or MRT_ERR_TOO_LARGE these return MRTH_ERR_INVALID_ARG; alignment and
+ * overlap, which matter to the device's 16-byte accesses and parallel lanes only, are not checked
+ * here. */
+int  mrth_temporal_motion(int32_t numPrimary, const int32_t* primarySlotToId, const void* primaryRays,
+                          const void* primaryResults, const int32_t* triangles, int64_t numTris,
+                          const float* vertices, const float* prevVertices, int64_t numVertices,
+                          int32_t numPixels, float* prevPosition);
+typedef struct mrth_temporal_params {
+    int32_t width;
+    int32_t height;
+    int32_t havePrev;
+    int32_t maxHistory;
+    float normalCos;
+    float sigmaPlane;
+    int32_t variant;             /* checked, otherwise ignored: the host has one statement */
+    int32_t reserved;
+    float prevWorldToScreen[16];
+    float prevSubpixel[2];
+    const float* image;
+    const void* guide;
+    const float* albedo;
+    const float* prevPosition;
+    const void* prevGuide;
+    const float* prevHistory;
+    float* history;
+    float* imageOut;
+    uint32_t* pixels;
+} mrth_temporal_params;
+int  mrth_temporal_accumulate(const mrth_temporal_params* params);
+
 /* RayBuffer::mortonSort (RayBuffer.cc:256-324): the CPU statement of mrt_ray_sort (mrt.h, which
  * states the key and the order), with the same arguments over HOST memory and no stream. outBox
  * is six host floats (lo.xyz, hi.xyz). The box and the keys are csrc/raysort_common.hpp's on both

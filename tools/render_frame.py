@@ -23,7 +23,10 @@ choose whether live paths are compacted between vertices (default: the Renderer'
 the paths started, over the summed time of all its traces. --denoise filters a path frame with
 the edge-avoiding wavelet denoiser (Renderer.denoise; --denoise-iterations, --sigma-color,
 --sigma-plane: default a fraction of the scene box's diagonal) before it is written; without it the
-file is what it always was.
+file is what it always was. --accumulate N renders N path frames of the camera with the renderer's
+consecutive seeds, blends each into the history of those before it (Renderer.accumulate) and writes
+the last; with --denoise the filter runs after the accumulation. The counts and the rate are the
+last frame's.
 """
 from __future__ import annotations
 
@@ -67,12 +70,18 @@ def main() -> int:
     ap.add_argument("--denoise-iterations", type=int, default=None, help="path, --denoise: a-trous iterations (0..8)")
     ap.add_argument("--sigma-color", type=float, default=None, help="path, --denoise: colour sigma of the demodulated image")
     ap.add_argument("--sigma-plane", type=float, default=None, help="path, --denoise: plane-distance sigma in scene units")
+    ap.add_argument("--accumulate", type=int, default=0, metavar="N",
+                    help="path: render N frames and write their temporal accumulation (Renderer.accumulate)")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--out", default="gpurun_out/frame.ppm")
     a = ap.parse_args()
     if a.denoise and a.ray_type != "path":
         ap.error("--denoise filters a --ray-type path frame")
+    if a.accumulate and a.ray_type != "path":
+        ap.error("--accumulate accumulates --ray-type path frames")
+    if a.accumulate < 0:
+        ap.error("--accumulate takes a number of frames")
     if not torch.cuda.is_available():
         raise SystemExit("render_frame needs a GPU")
     scene = mrt.Scene.from_obj(a.obj) if a.obj else mrt.Scene.synthetic(a.scene, 0, 1)
@@ -93,26 +102,31 @@ def main() -> int:
         light_radius = light_radius if light_radius is not None else float(0.02 * ((hi - lo) ** 2).sum() ** 0.5)
     r.set_params(rt, 1 if rt == RAY_PRIMARY else a.samples, ao_radius, light_pos=light or (0.0, 0.0, 0.0),
                  light_radius=light_radius or 0.0, depth=a.depth, light_color=a.light_color, sky=a.sky, compact=a.compact)
-    r.begin_frame(cam, w, h)
-    counted = r.total_num_rays()
     pixels = torch.zeros(w * h, dtype=torch.int32, device="cuda")
-    image = torch.zeros((w * h, 4), dtype=torch.float32, device="cuda") if a.denoise else None
-    ms, batches, live = 0.0, 0, None
-    while r.next_batch():
-        ms += r.trace_batch()
-        r.update_result(pixels, image=image)
-        batches += 1
-        live = list(r.path_stats) if rt == RAY_PATH else None
+    image = torch.zeros((w * h, 4), dtype=torch.float32, device="cuda") if a.denoise or a.accumulate else None
+    blended = torch.zeros((w * h, 4), dtype=torch.float32, device="cuda") if a.denoise and a.accumulate else None
+    for _ in range(max(a.accumulate, 1)):
+        r.begin_frame(cam, w, h)
+        counted = r.total_num_rays()
+        ms, batches, live = 0.0, 0, None
+        while r.next_batch():
+            ms += r.trace_batch()
+            r.update_result(pixels, image=image)
+            batches += 1
+            live = list(r.path_stats) if rt == RAY_PATH else None
+        if a.accumulate:
+            r.accumulate(image, pixels=pixels, image_out=blended)
     if a.denoise:
         settings = {k: v for k, v in (("iterations", a.denoise_iterations), ("sigma_color", a.sigma_color)) if v is not None}
-        r.denoise(image, pixels=pixels, sigma_plane=a.sigma_plane, **settings)
+        r.denoise(blended if a.accumulate else image, pixels=pixels, sigma_plane=a.sigma_plane, **settings)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     mrt.write_ppm(a.out, pixels.cpu().numpy(), w, h)
     print(json.dumps({"scene": a.obj or a.scene, "camera": a.camera, "ray_type": a.ray_type, "width": w, "height": h,
                       "samples": r.num_samples, "light": light, "light_radius": light_radius, "batches": batches,
                       **({"depth": a.depth, "compact": r.compact, "live_last_batch": live} if rt == RAY_PATH else {}),
-                      **({"denoised": True} if a.denoise else {}), "trace_ms": round(ms, 4), "rays_counted": counted,
+                      **({"denoised": True} if a.denoise else {}),
+                      **({"accumulated": a.accumulate} if a.accumulate else {}), "trace_ms": round(ms, 4), "rays_counted": counted,
                       "mrays_per_s": round(counted / ms / 1e3, 2) if ms > 0 else None, "image": a.out}))
     return 0
 
