@@ -1,6 +1,7 @@
-// api_common.hpp — what the C-ABI files (mrt_api.cpp, bind_api.cpp, refit_api.cpp, build_api.cpp,
-// derive_api.cpp, frame_api.cpp, scene_api.cpp, light_api.cpp, path_api.cpp, denoise_api.cpp, compat_api.cpp) share: the error returns, the device guard, and the owners of
-// the device memory, the stream-ordered scratch and the events the library allocates.
+// api_common.hpp — what the C-ABI files (every *_api.cpp) share on the HIP side: the error returns,
+// the device guard, the owners of the device memory, the stream-ordered scratch and the events the
+// library allocates, and the outcome of an export's launches. The pointer checks that need no HIP
+// are in api_checks.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -96,6 +97,17 @@ struct StreamScratch {
         return static_cast<T*>(p);
     }
 };
+
+// The outcome of an export's launches.
+inline int launched(hipError_t launch, const char* what) { return launch == hipSuccess ? MRT_OK : hipFail(launch, what); }
+
+// The outcome of launches that used stream-ordered scratch: the free is enqueued after them in
+// any case, and a launch error is reported in preference to the free's.
+inline int launched(hipError_t launch, const char* what, StreamScratch& scratch, const char* whatFree) {
+    const hipError_t f = scratch.release();
+    if (launch != hipSuccess) return hipFail(launch, what);
+    return f == hipSuccess ? MRT_OK : hipFail(f, whatFree);
+}
 
 // A hipEvent_t, destroyed with its owner. Move-only.
 struct Event {

@@ -4,41 +4,16 @@
 // caller's stream; nothing waits on the host, nothing is allocated and no state outlives a call.
 #include <cstdint>
 
+#include "api_checks.hpp"
 #include "api_common.hpp"
 #include "denoise_kernel.hpp"
 #include "denoise_plan.hpp"
 
+using mrt::aligned16;
+using mrt::any_overlap;
 using mrt::fail;
-using mrt::hipFail;
-
-namespace {
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-struct Span {
-    const void* p;
-    int64_t bytes;
-};
-
-bool overlap(const Span& a, const Span& b) {
-    if (!a.p || !b.p || a.bytes <= 0 || b.bytes <= 0) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
-    return a0 < b0 + (uintptr_t)b.bytes && b0 < a0 + (uintptr_t)a.bytes;
-}
-
-// No output may overlap an input or another output.
-template <size_t NI, size_t NO>
-bool any_overlap(const Span (&ins)[NI], const Span (&outs)[NO]) {
-    for (size_t i = 0; i < NO; i++) {
-        for (const Span& in : ins)
-            if (overlap(outs[i], in)) return true;
-        for (size_t j = i + 1; j < NO; j++)
-            if (overlap(outs[i], outs[j])) return true;
-    }
-    return false;
-}
-
-}  // namespace
+using mrt::launched;
+using mrt::Span;
 
 extern "C" {
 
@@ -69,7 +44,7 @@ int mrt_denoise_features(int32_t numPrimary, const int32_t* primarySlotToId, con
     a.guide = static_cast<float4*>(guide);
     a.albedo = reinterpret_cast<float4*>(albedo);
     const hipError_t e = mrt::launch_denoise_features(a, plan.grid, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? MRT_OK : hipFail(e, "denoise features launch");
+    return launched(e, "denoise features launch");
 }
 
 int mrt_denoise_filter(const mrt_denoise_params* q, void* stream) {
@@ -117,7 +92,7 @@ int mrt_denoise_filter(const mrt_denoise_params* q, void* stream) {
         else e = mrt::launch_denoise_filter(a, it.grid, s);
         in = pingpong[k & 1];
     }
-    return e == hipSuccess ? MRT_OK : hipFail(e, "denoise filter launch");
+    return launched(e, "denoise filter launch");
 }
 
 }  // extern "C"

@@ -29,41 +29,26 @@
 #include "denoise_kernel.hpp"
 
 #include "denoise_limits.hpp"
+#include "record_device.hpp"
 
 namespace mrt {
 namespace {
 
 using namespace denoise;
 
-__device__ inline Guide load_guide(const float4* guide, int q) {
-    const float4 lo = guide[2 * (int64_t)q], hi = guide[2 * (int64_t)q + 1];
-    return Guide{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-}
-
-__device__ inline Color load_color(const float4* image, int q) {
-    const float4 v = image[q];
-    return Color{v.x, v.y, v.z, v.w};
-}
-
-__device__ inline float4 as_float4(const Color& c) { return make_float4(c.r, c.g, c.b, c.a); }
-
 struct FeaturesArgs : DenoiseFeaturesLaunch {};
 
 __global__ __launch_bounds__(kThreads) void features_kernel(FeaturesArgs a) {
-    const int i = (int)(blockIdx.x * kThreads + threadIdx.x);
-    if (i >= a.numPrimary) return;
-    const int32_t p = a.primarySlotToId[i];
-    if (p < 0 || p >= a.numPixels) return;
-    const float4* r = reinterpret_cast<const float4*>(a.primaryRays + i);
-    const float4 lo = r[0], hi = r[1];
-    const int4 res = a.primaryResults[i];
+    PrimarySlot s;
+    if (!load_primary_slot((int)(blockIdx.x * kThreads + threadIdx.x), a.numPrimary, a.primarySlotToId, a.numPixels,
+                           a.primaryRays, a.primaryResults, s))
+        return;
     Guide g;
     Color albedo;
-    features_one(rg::RayRec{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}, res.x, __int_as_float(res.y), a.triNormals,
-                 a.triMaterialColor, a.numTris, g, albedo);
-    a.guide[2 * (int64_t)p] = make_float4(g.nx, g.ny, g.nz, g.hit);
-    a.guide[2 * (int64_t)p + 1] = make_float4(g.px, g.py, g.pz, g.pad);
-    a.albedo[p] = as_float4(albedo);
+    features_one(s.ray, s.id, s.t, a.triNormals, a.triMaterialColor, a.numTris, g, albedo);
+    a.guide[2 * (int64_t)s.pixel] = make_float4(g.nx, g.ny, g.nz, g.hit);
+    a.guide[2 * (int64_t)s.pixel + 1] = make_float4(g.px, g.py, g.pz, g.pad);
+    a.albedo[s.pixel] = as_float4(albedo);
 }
 
 struct FilterArgs : DenoiseFilterLaunch {};
@@ -78,14 +63,14 @@ struct GlobalSource {
     __device__ Guide guide(int x, int y) const { return load_guide(guides, y * width + x); }
     __device__ Color color(int x, int y, bool hit) const {
         const int q = y * width + x;
-        const Color c = load_color(in, q);
+        const Color c = as_color(in[q]);
         if (!First || !hit) return c;
-        return demodulate(c, load_color(albedo, q), true);
+        return demodulate(c, as_color(albedo[q]), true);
     }
 };
 
 __device__ inline void write_last(const FilterArgs& a, int p, const Color& c, bool hit) {
-    const Color r = hit ? remodulate(c, load_color(a.albedo, p), true) : c;
+    const Color r = hit ? remodulate(c, as_color(a.albedo[p]), true) : c;
     if (a.out) a.out[p] = as_float4(r);
     if (a.pixels) a.pixels[p] = pixel_of(r);
 }
@@ -109,13 +94,9 @@ struct TileSource {
     __device__ int at(int x, int y) const { return ((y - yOrigin) >> shift) * rowWords + (x - xOrigin); }
     __device__ Guide guide(int x, int y) const {
         const int i = at(x, y);
-        const float4 lo = lds[i], hi = lds[plane + i];
-        return Guide{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        return as_guide(lds[i], lds[plane + i]);
     }
-    __device__ Color color(int x, int y, bool) const {
-        const float4 v = lds[2 * plane + at(x, y)];
-        return Color{v.x, v.y, v.z, v.w};
-    }
+    __device__ Color color(int x, int y, bool) const { return as_color(lds[2 * plane + at(x, y)]); }
 };
 
 template <bool First, bool Last>
@@ -135,8 +116,8 @@ __global__ __launch_bounds__(kThreads) void filter_tiled_kernel(FilterArgs a) {
             const int q = y * a.width + x;
             lo = a.guide[2 * (int64_t)q];
             hi = a.guide[2 * (int64_t)q + 1];
-            Color v = load_color(a.in, q);
-            if (First && lo.w != 0.0f) v = demodulate(v, load_color(a.albedo, q), true);
+            Color v = as_color(a.in[q]);
+            if (First && lo.w != 0.0f) v = demodulate(v, as_color(a.albedo[q]), true);
             c = as_float4(v);
         }
         lds[i] = lo;

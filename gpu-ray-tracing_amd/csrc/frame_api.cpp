@@ -17,18 +17,9 @@
 
 using mrt::fail;
 using mrt::hipFail;
+using mrt::launched;
 
 namespace {
-
-// The outcome of launches that used stream-ordered scratch: the free is enqueued after them in
-// any case, and a launch error is reported in preference to the free's.
-int launched(hipError_t launch, const char* what, mrt::StreamScratch& scratch, const char* whatFree) {
-    const hipError_t f = scratch.release();
-    if (launch != hipSuccess) return hipFail(launch, what);
-    return f == hipSuccess ? MRT_OK : hipFail(f, whatFree);
-}
-
-int launched(hipError_t launch, const char* what) { return launch == hipSuccess ? MRT_OK : hipFail(launch, what); }
 
 // Whether [p, p + bytes) lies in memory the device can address, as far as the runtime can tell
 // without touching the stream: p is registered with it (device, managed or pinned host memory)

@@ -8,29 +8,12 @@
 #include "../denoise_common.hpp"
 #include "../denoise_plan.hpp"
 #include "host_error.hpp"
+#include "records.hpp"
 
 namespace mrt {
 namespace {
 
-struct Result {   // RayResult (reference Util.hh:78-89)
-    int32_t id;
-    float t;
-    int32_t pad[2];
-};
-static_assert(sizeof(Result) == 16 && sizeof(rg::RayRec) == 32 && sizeof(denoise::Guide) == 32 && sizeof(denoise::Color) == 16,
-              "record sizes");
-
-template <class T>
-T get(const void* base, int64_t at) {
-    T v;
-    std::memcpy(&v, static_cast<const char*>(base) + (int64_t)sizeof(T) * at, sizeof(T));
-    return v;
-}
-
-template <class T>
-void put(void* base, int64_t at, const T& v) {
-    std::memcpy(static_cast<char*>(base) + (int64_t)sizeof(T) * at, &v, sizeof(T));
-}
+static_assert(sizeof(rg::RayRec) == 32 && sizeof(denoise::Guide) == 32 && sizeof(denoise::Color) == 16, "record sizes");
 
 // c_k of a pixel, from host memory: iteration 0 demodulates the frame's image on the way.
 struct HostSource {
@@ -39,18 +22,18 @@ struct HostSource {
     const float* albedo;
     int width;
     bool first;
-    denoise::Guide guide(int x, int y) const { return get<denoise::Guide>(guides, y * width + x); }
+    denoise::Guide guide(int x, int y) const { return get_record<denoise::Guide>(guides, y * width + x); }
     denoise::Color color(int x, int y, bool hit) const {
         const int q = y * width + x;
-        const denoise::Color c = get<denoise::Color>(in, q);
+        const denoise::Color c = get_record<denoise::Color>(in, q);
         if (!first || !hit) return c;
-        return denoise::demodulate(c, get<denoise::Color>(albedo, q), true);
+        return denoise::demodulate(c, get_record<denoise::Color>(albedo, q), true);
     }
 };
 
 void write_last(const mrth_denoise_params& a, int p, const denoise::Color& c, bool hit) {
-    const denoise::Color r = hit ? denoise::remodulate(c, get<denoise::Color>(a.albedo, p), true) : c;
-    if (a.imageOut) put(a.imageOut, p, r);
+    const denoise::Color r = hit ? denoise::remodulate(c, get_record<denoise::Color>(a.albedo, p), true) : c;
+    if (a.imageOut) put_record(a.imageOut, p, r);
     if (a.pixels) a.pixels[p] = denoise::pixel_of(r);
 }
 
@@ -70,13 +53,13 @@ int mrth_denoise_features(int32_t numPrimary, const int32_t* primarySlotToId, co
     for (int32_t i = 0; i < numPrimary; i++) {
         const int32_t p = primarySlotToId[i];
         if (p < 0 || p >= numPixels) continue;
-        const mrt::Result res = mrt::get<mrt::Result>(primaryResults, i);
+        const mrt::RayResult res = mrt::get_record<mrt::RayResult>(primaryResults, i);
         mrt::denoise::Guide g;
         mrt::denoise::Color a;
-        mrt::denoise::features_one(mrt::get<mrt::rg::RayRec>(primaryRays, i), res.id, res.t, triNormals, triMaterialColor,
+        mrt::denoise::features_one(mrt::get_record<mrt::rg::RayRec>(primaryRays, i), res.id, res.t, triNormals, triMaterialColor,
                                    numTris, g, a);
-        mrt::put(guide, p, g);
-        mrt::put(albedo, p, a);
+        mrt::put_record(guide, p, g);
+        mrt::put_record(albedo, p, a);
     }
     return MRTH_OK;
 }
@@ -112,7 +95,7 @@ int mrth_denoise_filter(const mrth_denoise_params* a) {
                     mrt::denoise::filter_pixel(src, x, y, w, h, 1 << k, plan.invPlane, plan.at[k].invColor2, a->normalSquarings);
                 const int p = y * w + x;
                 if (last) mrt::write_last(*a, p, c, mrt::denoise::is_hit(src.guide(x, y)));
-                else mrt::put(out, p, c);
+                else mrt::put_record(out, p, c);
             }
         }
         in = out;

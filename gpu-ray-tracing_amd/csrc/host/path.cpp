@@ -8,28 +8,12 @@
 #include "../path_common.hpp"
 #include "../path_plan.hpp"
 #include "host_error.hpp"
+#include "records.hpp"
 
 namespace mrt {
 namespace {
 
-struct Result {   // RayResult (reference Util.hh:78-89)
-    int32_t id;
-    float t;
-    int32_t pad[2];
-};
-static_assert(sizeof(Result) == 16 && sizeof(rg::RayRec) == 32 && sizeof(path::State) == 16, "record sizes");
-
-template <class T>
-T get(const void* base, int64_t at) {
-    T v;
-    std::memcpy(&v, static_cast<const char*>(base) + (int64_t)sizeof(T) * at, sizeof(T));
-    return v;
-}
-
-template <class T>
-void put(void* base, int64_t at, const T& v) {
-    std::memcpy(static_cast<char*>(base) + (int64_t)sizeof(T) * at, &v, sizeof(T));
-}
+static_assert(sizeof(rg::RayRec) == 32 && sizeof(path::State) == 16, "record sizes");
 
 struct Pending {
     float v[4];
@@ -65,27 +49,27 @@ void path_extend(const mrth_path_extend_params& a) {
         if (a.vertex == 0) {
             at = slot / a.numSamples;
         } else {
-            state = get<path::State>(a.inState, slot);
+            state = get_record<path::State>(a.inState, slot);
             live = path::owns(state.task, a.numPaths);
         }
         path::Step st;
         st.survivor = st.escaped = false;
         if (live) {
-            const Result res = get<Result>(a.inResults, at);
-            path::extend(p, get<rg::RayRec>(a.inRays, at), res.id, res.t, state, st);
+            const RayResult res = get_record<RayResult>(a.inResults, at);
+            path::extend(p, get_record<rg::RayRec>(a.inRays, at), res.id, res.t, state, st);
         }
         if (live && st.survivor) {
             const int64_t dest = a.compact ? survivors : slot;
-            put(a.outShadowRays, dest, st.shadow);
-            put(a.outPending, dest, Pending{{st.pending[0], st.pending[1], st.pending[2], 0.0f}});
-            if (a.vertex < a.depth) put(a.outRays, dest, st.bounce);
-            put(a.outState, dest, st.state);
+            put_record(a.outShadowRays, dest, st.shadow);
+            put_record(a.outPending, dest, Pending{{st.pending[0], st.pending[1], st.pending[2], 0.0f}});
+            if (a.vertex < a.depth) put_record(a.outRays, dest, st.bounce);
+            put_record(a.outState, dest, st.state);
             survivors++;
         } else if (!a.compact) {
-            put(a.outShadowRays, slot, path::dead_ray());
-            put(a.outPending, slot, Pending{{0.0f, 0.0f, 0.0f, 0.0f}});
-            if (a.vertex < a.depth) put(a.outRays, slot, path::dead_ray());
-            put(a.outState, slot, path::dead_state());
+            put_record(a.outShadowRays, slot, path::dead_ray());
+            put_record(a.outPending, slot, Pending{{0.0f, 0.0f, 0.0f, 0.0f}});
+            if (a.vertex < a.depth) put_record(a.outRays, slot, path::dead_ray());
+            put_record(a.outState, slot, path::dead_state());
         }
         if (live && st.escaped) add3(a.radiance, st.task, st.add);
     }
@@ -118,9 +102,9 @@ int mrth_path_accumulate(int32_t numSlots, int32_t numPaths, const void* state, 
     if (!state || !pending || !shadowResults || !radiance)
         return mrt::host_fail(MRTH_ERR_INVALID_ARG, "path_accumulate: null argument");
     for (int32_t slot = 0; slot < numSlots; slot++) {
-        const int32_t task = mrt::get<mrt::path::State>(state, slot).task;
-        if (!mrt::path::owns(task, numPaths) || mrt::get<mrt::Result>(shadowResults, slot).id != -1) continue;
-        const mrt::Pending p = mrt::get<mrt::Pending>(pending, slot);
+        const int32_t task = mrt::get_record<mrt::path::State>(state, slot).task;
+        if (!mrt::path::owns(task, numPaths) || mrt::get_record<mrt::RayResult>(shadowResults, slot).id != -1) continue;
+        const mrt::Pending p = mrt::get_record<mrt::Pending>(pending, slot);
         mrt::add3(radiance, task, p.v);
     }
     return MRTH_OK;
@@ -137,7 +121,7 @@ int mrth_path_resolve(int32_t numSamples, int32_t firstPrimary, int32_t numPrima
         const int64_t slot = firstPrimary + i;
         const int32_t pixel = primarySlotToId[slot];
         float v[4];
-        if (mrt::get<mrt::Result>(primaryResults, slot).id == -1) mrt::path::background(v);
+        if (mrt::get_record<mrt::RayResult>(primaryResults, slot).id == -1) mrt::path::background(v);
         else mrt::path::resolve_one(radiance + 4 * i * numSamples, numSamples, v);
         pixels[pixel] = mrt::light::to_abgr(v);
         if (image)

@@ -1,8 +1,9 @@
-// raygen.hpp — host ray generation and the reference's Ray / RayResult records.
+// raygen.hpp — host ray generation and the reference's Ray record (RayResult: records.hpp).
 #pragma once
 #include <cstdint>
 #include <vector>
 
+#include "records.hpp"
 #include "scene.hpp"
 
 namespace mrt {
@@ -13,15 +14,6 @@ struct Ray {
     float dx, dy, dz, tmax;
 };
 static_assert(sizeof(Ray) == 32, "Ray must be 32 bytes");
-
-// reference src/rt/Util.hh:79-89 — 16 B; the trace writes {id, t} only.
-struct RayResult {
-    int32_t id;
-    float t;
-    int32_t padA;
-    int32_t padB;
-};
-static_assert(sizeof(RayResult) == 16, "RayResult must be 16 bytes");
 
 Mat4f nscreen_to_world(const Camera& cam, int w, int h);
 std::vector<int32_t> pixel_table(int w, int h);

@@ -8,30 +8,12 @@
 #include "../temporal_common.hpp"
 #include "../temporal_plan.hpp"
 #include "host_error.hpp"
+#include "records.hpp"
 
 namespace mrt {
 namespace {
 
-struct TemporalResult {   // RayResult (reference Util.hh:78-89)
-    int32_t id;
-    float t;
-    int32_t pad[2];
-};
-static_assert(sizeof(TemporalResult) == 16 && sizeof(rg::RayRec) == 32 && sizeof(temporal::Guide) == 32 &&
-                  sizeof(temporal::Color) == 16,
-              "record sizes");
-
-template <class T>
-T get_record(const void* base, int64_t at) {
-    T v;
-    std::memcpy(&v, static_cast<const char*>(base) + (int64_t)sizeof(T) * at, sizeof(T));
-    return v;
-}
-
-template <class T>
-void put_record(void* base, int64_t at, const T& v) {
-    std::memcpy(static_cast<char*>(base) + (int64_t)sizeof(T) * at, &v, sizeof(T));
-}
+static_assert(sizeof(rg::RayRec) == 32 && sizeof(temporal::Guide) == 32 && sizeof(temporal::Color) == 16, "record sizes");
 
 struct TemporalHostSource {
     const mrth_temporal_params& a;
@@ -60,7 +42,7 @@ int mrth_temporal_motion(int32_t numPrimary, const int32_t* primarySlotToId, con
     for (int32_t i = 0; i < numPrimary; i++) {
         const int32_t p = primarySlotToId[i];
         if (p < 0 || p >= numPixels) continue;
-        const mrt::TemporalResult res = mrt::get_record<mrt::TemporalResult>(primaryResults, i);
+        const mrt::RayResult res = mrt::get_record<mrt::RayResult>(primaryResults, i);
         mrt::put_record(prevPosition, p,
                         mrt::temporal::motion_one(mrt::get_record<mrt::rg::RayRec>(primaryRays, i), res.id, res.t, triangles,
                                                   numTris, vertices, prevVertices, numVertices));

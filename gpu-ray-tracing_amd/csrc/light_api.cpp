@@ -6,22 +6,16 @@
 //   mrt_raygen_shadow  <- RayGen::shadow (reference RayGen.cc:147-183, commented out there)
 #include <cstdint>
 
+#include "api_checks.hpp"
 #include "api_common.hpp"
 #include "frame_plan.hpp"
 #include "light_kernel.hpp"
 #include "raygen_kernel.hpp"   // launch_seed_table
 
+using mrt::aligned16;   // rays are read and written as 16-byte halves
 using mrt::fail;
 using mrt::hipFail;
-
-namespace {
-
-int launched(hipError_t launch, const char* what) { return launch == hipSuccess ? MRT_OK : hipFail(launch, what); }
-
-// Rays are read and written as 16-byte halves.
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
+using mrt::launched;
 
 extern "C" {
 
@@ -85,9 +79,7 @@ int mrt_raygen_shadow_blocks(const void* inRays, const void* inResults, int32_t 
     a.seedTable = table.as<uint32_t>();
     hipError_t e = mrt::launch_seed_table(table.as<uint32_t>(), batchSeeds, p.needBatches, s);
     if (e == hipSuccess) e = mrt::launch_shadow_blocks(a, grid, s);
-    const hipError_t f = table.release();
-    if (e != hipSuccess) return hipFail(e, "raygen shadow blocks launch");
-    return f == hipSuccess ? MRT_OK : hipFail(f, "hipFreeAsync(batch seeds)");
+    return launched(e, "raygen shadow blocks launch", table, "hipFreeAsync(batch seeds)");
 }
 
 int mrt_reconstruct_lit(int32_t numRaysPerPrimary, int32_t firstPrimary, int32_t numPrimary,

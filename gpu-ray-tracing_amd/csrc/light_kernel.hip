@@ -15,6 +15,7 @@
 #include "light_kernel.hpp"
 
 #include "light_common.hpp"
+#include "record_device.hpp"
 
 namespace mrt {
 namespace {
@@ -28,16 +29,9 @@ struct InputRay {
 };
 
 __device__ inline InputRay load_input(const rg::RayRec* rays, const int2* results, int p) {
-    const float4* r = reinterpret_cast<const float4*>(rays + p);
-    const float4 lo = r[0], hi = r[1];
-    const int2 res = results[2 * (int64_t)p];
-    return InputRay{rg::RayRec{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}, res.x, __int_as_float(res.y)};
-}
-
-__device__ inline void store_ray(rg::RayRec* out, int64_t at, const rg::RayRec& r) {
-    float4* o = reinterpret_cast<float4*>(out + at);
-    o[0] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-    o[1] = make_float4(r.dx, r.dy, r.dz, r.tmax);
+    const rg::RayRec ray = load_ray(rays, p);
+    const int2 res = results[2 * (int64_t)p];   // the result's first 8 of 16 bytes
+    return InputRay{ray, res.x, __int_as_float(res.y)};
 }
 
 struct ShadowArgs : ShadowLaunch {};

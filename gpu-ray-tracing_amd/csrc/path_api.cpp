@@ -4,32 +4,16 @@
 // enqueued on the caller's stream; nothing waits on the host and no state outlives a call.
 #include <cstdint>
 
+#include "api_checks.hpp"
 #include "api_common.hpp"
 #include "path_kernel.hpp"
 #include "path_plan.hpp"
 
+using mrt::aligned16;   // rays, states, pending contributions and radiances move as 16-byte words
 using mrt::fail;
 using mrt::hipFail;
-
-namespace {
-
-int launched(hipError_t launch, const char* what) { return launch == hipSuccess ? MRT_OK : hipFail(launch, what); }
-
-// Rays, states, pending contributions and radiances move as 16-byte words.
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-struct Span {
-    const void* p;
-    int64_t bytes;
-};
-
-bool overlap(const Span& a, const Span& b) {
-    if (!a.p || !b.p || a.bytes <= 0 || b.bytes <= 0) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
-    return a0 < b0 + (uintptr_t)b.bytes && b0 < a0 + (uintptr_t)a.bytes;
-}
-
-}  // namespace
+using mrt::launched;
+using mrt::Span;
 
 extern "C" {
 
@@ -50,12 +34,8 @@ int mrt_path_extend(const mrt_path_extend_params* q, void* stream) {
     const Span ins[] = {{q->inRays, 32 * inputs}, {q->inResults, 16 * inputs}, {first ? nullptr : q->inState, 16 * n}};
     const Span outs[] = {{q->outShadowRays, 32 * n}, {q->outPending, 16 * n}, {last ? nullptr : q->outRays, 32 * n},
                          {q->outState, 16 * n}, {q->radiance, 16 * (int64_t)q->numPaths}, {q->liveCount, 4}};
-    for (size_t i = 0; i < sizeof(outs) / sizeof(outs[0]); i++) {
-        for (const Span& in : ins)
-            if (overlap(outs[i], in)) return fail(MRT_ERR_INVALID_ARG, "an output buffer overlaps an input buffer");
-        for (size_t j = i + 1; j < sizeof(outs) / sizeof(outs[0]); j++)
-            if (overlap(outs[i], outs[j])) return fail(MRT_ERR_INVALID_ARG, "two output buffers overlap");
-    }
+    if (mrt::output_overlaps_input(ins, outs)) return fail(MRT_ERR_INVALID_ARG, "an output buffer overlaps an input buffer");
+    if (mrt::outputs_overlap(outs)) return fail(MRT_ERR_INVALID_ARG, "two output buffers overlap");
     mrt::PathExtendLaunch a{};
     a.p.vertex = q->vertex;
     a.p.depth = q->depth;
@@ -90,9 +70,7 @@ int mrt_path_extend(const mrt_path_extend_params* q, void* stream) {
     hipError_t e = mrt::launch_path_count(a, plan.grid, s);
     if (e == hipSuccess) e = mrt::launch_path_scan(a.counts, plan.grid, a.liveCount, s);
     if (e == hipSuccess) e = mrt::launch_path_extend(a, plan.grid, s);
-    const hipError_t f = counts.release();
-    if (e != hipSuccess) return hipFail(e, "path extend launch");
-    return f == hipSuccess ? MRT_OK : hipFail(f, "hipFreeAsync(path counts)");
+    return launched(e, "path extend launch", counts, "hipFreeAsync(path counts)");
 }
 
 int mrt_path_accumulate(int32_t numSlots, int32_t numPaths, const void* state, const void* pending,

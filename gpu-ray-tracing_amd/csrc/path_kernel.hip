@@ -22,23 +22,12 @@
 #include "path_kernel.hpp"
 
 #include "path_limits.hpp"
+#include "record_device.hpp"
 
 namespace mrt {
 namespace {
 
 using namespace path;
-
-__device__ inline rg::RayRec load_ray(const rg::RayRec* rays, int64_t at) {
-    const float4* r = reinterpret_cast<const float4*>(rays + at);
-    const float4 lo = r[0], hi = r[1];
-    return rg::RayRec{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-}
-
-__device__ inline void store_ray(rg::RayRec* out, int64_t at, const rg::RayRec& r) {
-    float4* o = reinterpret_cast<float4*>(out + at);
-    o[0] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-    o[1] = make_float4(r.dx, r.dy, r.dz, r.tmax);
-}
 
 __device__ inline State load_state(const State* states, int64_t at) {
     const int4 v = reinterpret_cast<const int4*>(states)[at];

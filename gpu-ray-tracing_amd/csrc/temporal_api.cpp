@@ -6,41 +6,16 @@
 #include <cstdint>
 
 #include "../../include/mrt_temporal.h"
+#include "api_checks.hpp"
 #include "api_common.hpp"
 #include "temporal_kernel.hpp"
 #include "temporal_plan.hpp"
 
+using mrt::aligned16;
+using mrt::any_overlap;
 using mrt::fail;
-using mrt::hipFail;
-
-namespace {
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-struct Span {
-    const void* p;
-    int64_t bytes;
-};
-
-bool overlap(const Span& a, const Span& b) {
-    if (!a.p || !b.p || a.bytes <= 0 || b.bytes <= 0) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
-    return a0 < b0 + (uintptr_t)b.bytes && b0 < a0 + (uintptr_t)a.bytes;
-}
-
-// No output may overlap an input or another output.
-template <size_t NI, size_t NO>
-bool any_overlap(const Span (&ins)[NI], const Span (&outs)[NO]) {
-    for (size_t i = 0; i < NO; i++) {
-        for (const Span& in : ins)
-            if (overlap(outs[i], in)) return true;
-        for (size_t j = i + 1; j < NO; j++)
-            if (overlap(outs[i], outs[j])) return true;
-    }
-    return false;
-}
-
-}  // namespace
+using mrt::launched;
+using mrt::Span;
 
 extern "C" {
 
@@ -73,7 +48,7 @@ int mrt_temporal_motion(int32_t numPrimary, const int32_t* primarySlotToId, cons
     a.prevVertices = prevVertices;
     a.prevPosition = reinterpret_cast<float4*>(prevPosition);
     const hipError_t e = mrt::launch_temporal_motion(a, plan.grid, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? MRT_OK : hipFail(e, "temporal motion launch");
+    return launched(e, "temporal motion launch");
 }
 
 int mrt_temporal_accumulate(const mrt_temporal_params* q, void* stream) {
@@ -116,7 +91,7 @@ int mrt_temporal_accumulate(const mrt_temporal_params* q, void* stream) {
     a.imageOut = reinterpret_cast<float4*>(q->imageOut);
     a.pixels = q->pixels;
     const hipError_t e = mrt::launch_temporal_accumulate(a, plan.grid, plan.tiled != 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? MRT_OK : hipFail(e, "temporal accumulate launch");
+    return launched(e, "temporal accumulate launch");
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 // the bits are the host's.
 #include "temporal_kernel.hpp"
 
+#include "record_device.hpp"
 #include "temporal_limits.hpp"
 
 namespace mrt {
@@ -26,27 +27,15 @@ namespace {
 
 using namespace temporal;
 
-__device__ inline Color as_color(const float4& v) { return Color{v.x, v.y, v.z, v.w}; }
-__device__ inline float4 as_float4(const Color& c) { return make_float4(c.r, c.g, c.b, c.a); }
-
-__device__ inline Guide load_guide(const float4* guide, int q) {
-    const float4 lo = guide[2 * (int64_t)q], hi = guide[2 * (int64_t)q + 1];
-    return Guide{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-}
-
 struct MotionArgs : TemporalMotionLaunch {};
 
 __global__ __launch_bounds__(kThreads) void motion_kernel(MotionArgs a) {
-    const int i = (int)(blockIdx.x * kThreads + threadIdx.x);
-    if (i >= a.numPrimary) return;
-    const int32_t p = a.primarySlotToId[i];
-    if (p < 0 || p >= a.numPixels) return;
-    const float4* r = reinterpret_cast<const float4*>(a.primaryRays + i);
-    const float4 lo = r[0], hi = r[1];
-    const int4 res = a.primaryResults[i];
-    const Color q = motion_one(rg::RayRec{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}, res.x, __int_as_float(res.y),
-                               a.triangles, a.numTris, a.vertices, a.prevVertices, a.numVertices);
-    a.prevPosition[p] = as_float4(q);
+    PrimarySlot s;
+    if (!load_primary_slot((int)(blockIdx.x * kThreads + threadIdx.x), a.numPrimary, a.primarySlotToId, a.numPixels,
+                           a.primaryRays, a.primaryResults, s))
+        return;
+    a.prevPosition[s.pixel] =
+        as_float4(motion_one(s.ray, s.id, s.t, a.triangles, a.numTris, a.vertices, a.prevVertices, a.numVertices));
 }
 
 struct AccumulateArgs : TemporalAccumulateLaunch {};
