@@ -603,6 +603,74 @@ def temporal_accumulate(image, guide, albedo, width: int, height: int, prev_guid
     return history, out, pixels
 
 
+def svgf_accumulate(image, guide, albedo, width: int, height: int, prev_guide=None, prev_history=None, prev_moments=None,
+                    prev_world_to_screen=None, prev_subpixel=(0.5, 0.5), prev_position=None, max_history: int = 32,
+                    normal_cos: float = 0.8, sigma_plane: float = 1.0, want_image: bool = True,
+                    want_pixels: bool = True, have_prev: bool | None = None):
+    """mrth_svgf_accumulate (the CPU statement of mrt_svgf_accumulate, whose bits it gives):
+    temporal_accumulate with the luminance moments carried along. have_prev None: whether
+    prev_guide, prev_history and prev_moments are given. Returns (history float32 [w*h, 4], moments
+    float32 [w*h, 4], image_out float32 [w*h, 4] or None, pixels uint32 [w*h] or None)."""
+    n = int(width) * int(height)
+    img = np.ascontiguousarray(image, np.float32).reshape(-1, 4)
+    gd = np.ascontiguousarray(guide, np.float32).reshape(-1, 8)
+    alb = np.ascontiguousarray(albedo, np.float32).reshape(-1, 4)
+    pg = None if prev_guide is None else np.ascontiguousarray(prev_guide, np.float32).reshape(-1, 8)
+    ph = None if prev_history is None else np.ascontiguousarray(prev_history, np.float32).reshape(-1, 4)
+    pm = None if prev_moments is None else np.ascontiguousarray(prev_moments, np.float32).reshape(-1, 4)
+    pp = None if prev_position is None else np.ascontiguousarray(prev_position, np.float32).reshape(-1, 4)
+    if width < 1 or height < 1 or any(a is not None and len(a) != n for a in (img, gd, alb, pg, ph, pm, pp)):
+        raise _lib.MrtError("svgf_accumulate: every buffer holds one entry per pixel of the frame")
+    p = _lib.SvgfAccumulateParams()
+    p.width, p.height, p.maxHistory = int(width), int(height), int(max_history)
+    p.havePrev = int(pg is not None and ph is not None and pm is not None) if have_prev is None else int(bool(have_prev))
+    p.normalCos, p.sigmaPlane = float(np.float32(normal_cos)), float(np.float32(sigma_plane))
+    m = np.zeros(16, np.float32) if prev_world_to_screen is None else np.asarray(prev_world_to_screen, np.float32).reshape(16)
+    for i in range(16):
+        p.prevWorldToScreen[i] = float(m[i])
+    p.prevSubpixel[0], p.prevSubpixel[1] = float(np.float32(prev_subpixel[0])), float(np.float32(prev_subpixel[1]))
+    history, moments = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+    out = np.zeros((n, 4), np.float32) if want_image else None
+    pixels = np.zeros(n, np.uint32) if want_pixels else None
+    p.image, p.guide, p.albedo = _ptr(img), _ptr(gd), _ptr(alb)
+    p.prevPosition = None if pp is None else _ptr(pp)
+    p.prevGuide, p.prevHistory = (None if pg is None else _ptr(pg)), (None if ph is None else _ptr(ph))
+    p.prevMoments = None if pm is None else _ptr(pm)
+    p.history, p.moments = _ptr(history), _ptr(moments)
+    p.imageOut, p.pixels = (None if out is None else _ptr(out)), (None if pixels is None else _ptr(pixels))
+    _lib.check_host(_lib.host_lib().mrth_svgf_accumulate(C.byref(p)))
+    return history, moments, out, pixels
+
+
+def svgf_filter(image, guide, albedo, moments, width: int, height: int, iterations: int = 5, sigma_luminance: float = 4.0,
+                sigma_plane: float = 1.0, normal_squarings: int = 7, want_image: bool = True, want_pixels: bool = True,
+                want_variance: bool = True):
+    """mrth_svgf_filter (the CPU statement of mrt_svgf_filter, whose bits it gives): the variance
+    of every pixel from its moments and the variance-guided a-trous filter over a width x height
+    accumulated image. Returns (image_out float32 [w*h, 4] or None, pixels uint32 [w*h] or None,
+    variance float32 [w*h] or None)."""
+    n = int(width) * int(height)
+    img = np.ascontiguousarray(image, np.float32).reshape(-1, 4)
+    gd = np.ascontiguousarray(guide, np.float32).reshape(-1, 8)
+    alb = np.ascontiguousarray(albedo, np.float32).reshape(-1, 4)
+    mom = np.ascontiguousarray(moments, np.float32).reshape(-1, 4)
+    if width < 1 or height < 1 or len(img) != n or len(gd) != n or len(alb) != n or len(mom) != n:
+        raise _lib.MrtError("svgf_filter: image, guide, albedo and moments hold one entry per pixel of the frame")
+    p = _lib.SvgfFilterParams()
+    p.width, p.height, p.iterations, p.normalSquarings = int(width), int(height), int(iterations), int(normal_squarings)
+    p.sigmaLuminance, p.sigmaPlane = float(np.float32(sigma_luminance)), float(np.float32(sigma_plane))
+    scratch = [np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)]
+    out = np.zeros((n, 4), np.float32) if want_image else None
+    pixels = np.zeros(n, np.uint32) if want_pixels else None
+    variance = np.zeros(n, np.float32) if want_variance else None
+    p.image, p.guide, p.albedo, p.moments = _ptr(img), _ptr(gd), _ptr(alb), _ptr(mom)
+    p.scratch[0], p.scratch[1] = _ptr(scratch[0]), _ptr(scratch[1])
+    p.imageOut, p.pixels = (None if out is None else _ptr(out)), (None if pixels is None else _ptr(pixels))
+    p.varianceOut = None if variance is None else _ptr(variance)
+    _lib.check_host(_lib.host_lib().mrth_svgf_filter(C.byref(p)))
+    return out, pixels, variance
+
+
 def ray_sort(rays, slot_to_id=None, drop_levels: int = 0, box: int = 0) -> dict:
     """RayBuffer::mortonSort on the host (mrth_ray_sort; the CPU statement of
     RayBuffer.morton_sort, whose bits it reproduces): the batch in the order of the reference's

@@ -21,7 +21,8 @@ light, batched and seeded like AO, reconstructed by DeviceReconstructor.reconstr
 A fifth, RAY_PATH, carries the same batches of primary hits through up to `depth` diffuse bounces
 with a light sample at every vertex (mrt.path.PathIntegrator): next_batch starts a
 batch's paths, trace_batch runs its vertices, update_result resolves it. accumulate blends the
-resolved frame into the history of the frames before it (mrt.temporal), denoise filters it.
+resolved frame into the history of the frames before it (mrt.temporal; DESIGN §18), denoise filters it;
+svgf does both with the luminance variance carried along to guide the filter (mrt.svgf).
 
 The reference draws every AO/diffuse batch seed from the C library's rand()
 (RayGen.cc:106; App never seeds it, so the sequence starts at glibc's
@@ -38,6 +39,7 @@ from . import _lib
 from .denoise import SIGMA_PLANE_FRACTION_DEFAULT, Denoiser
 from .host import Camera, Scene
 from .path import PathIntegrator
+from . import svgf as _svgf
 from . import temporal as _temporal
 from .raygen import RAY_AO, RAY_DIFFUSE, RAY_PATH, RAY_PRIMARY, RAY_SHADOW, DeviceRayGen, DeviceReconstructor
 from .tracer import RayBuffer, Tracer, _on_stream
@@ -113,6 +115,11 @@ class Renderer:
         # last call (_vertices) and those the last accumulated frame saw (_motion_from, until the
         # next accumulate has reprojected through them)
         self._temporal: _temporal.TemporalAccumulator | None = None
+        # svgf: its own accumulator (with moments) and accumulated image; the vertex bookkeeping is
+        # shared, and _accumulated_by is whichever of the two saw the last frame: the other's history is stale
+        self._svgf: _svgf.SvgfAccumulator | None = None
+        self._svgf_image: torch.Tensor | None = None
+        self._accumulated_by: _temporal.TemporalAccumulator | None = None
         self._vertices = self._motion_from = None
         self._moved_unseen = False    # a set_vertices before the first accumulate: its vertices were not kept
         self._temporal_tris = -1      # the triangle count the history was accumulated over
@@ -188,7 +195,7 @@ class Renderer:
                 v = vertices.to(dev, torch.float32).contiguous().view(-1, 3)
             else:
                 v = torch.from_numpy(np.array(vertices, np.float32).reshape(-1, 3)).to(dev)
-            if self._temporal is not None:   # the previous frame's vertices, for accumulate's reprojection
+            if self._temporal is not None or self._svgf is not None:   # the previous frame's vertices, for the reprojection
                 self._keep_motion(v, dev)
             else:
                 self._moved_unseen = True
@@ -210,14 +217,16 @@ class Renderer:
         return out
 
     def _keep_motion(self, v: torch.Tensor, dev) -> None:
-        """set_vertices after the first accumulate(): a device clone of v (made on the stream
+        """set_vertices after the first accumulate() or svgf(): a device clone of v (made on the stream
         set_vertices runs on) becomes the current vertices; the ones before it, those the last
         accumulated frame saw, are kept until the next accumulate. Before any set_vertices they are
         the scene's vertices as loaded. Vertices that an earlier set_vertices brought and nobody
         kept cannot be reprojected from: the history starts over."""
         if self._vertices is None:
             if self._moved_unseen:
-                self._temporal.reset()
+                for acc in (self._temporal, self._svgf):
+                    if acc is not None:
+                        acc.reset()
             else:
                 self._vertices = torch.from_numpy(self.scene.arrays()[0]).to(dev)
         if self._motion_from is None:
@@ -408,27 +417,68 @@ class Renderer:
         as loaded). reset=True, another frame size and another triangle count (a Tracer.build in
         between) start a new history. It takes no stream: it runs on torch's current stream, so to
         use a side stream s call it under `with torch.cuda.stream(s)`. Nothing waits on the host."""
-        if self.ray_type != RAY_PATH:
-            raise _lib.MrtError("Renderer.accumulate: only a RAY_PATH frame is accumulated")
-        if self.primary is None or self._recon is None:
-            raise _lib.MrtError("Renderer.accumulate before begin_frame and the frame's batches")
+        self._check_accumulable("accumulate")
         if self._temporal is None:
             self._temporal = _temporal.TemporalAccumulator(self.gen.device)
+        return self._accumulate_with(self._temporal, image, pixels, image_out, sigma_plane, reset, settings)
+
+    def _check_accumulable(self, what: str) -> None:
+        if self.ray_type != RAY_PATH:
+            raise _lib.MrtError(f"Renderer.{what}: only a RAY_PATH frame is accumulated")
+        if self.primary is None or self._recon is None:
+            raise _lib.MrtError(f"Renderer.{what} before begin_frame and the frame's batches")
+
+    def _accumulate_with(self, acc, image, pixels, image_out, sigma_plane, reset, settings):
+        """accumulate's and svgf's common part: the restart rules, the vertices the last accumulated
+        frame saw, and acc.accumulate. A frame that the other accumulator saw last restarts acc's
+        history: what acc holds is from before that frame."""
         material = self._recon.material
-        if reset or material.numel() != self._temporal_tris:
-            self._temporal.reset()
+        if reset or material.numel() != self._temporal_tris or self._accumulated_by is not acc:
+            acc.reset()
         if sigma_plane is None:
             sigma_plane = self._default_sigma_plane(_temporal.SIGMA_PLANE_FRACTION_DEFAULT)
         prev = self._motion_from
         if prev is not None and (prev.numel() != self._vertices.numel() or self._triangles.numel() != 3 * material.numel()):
             prev = None               # another mesh: nothing to reproject through
-            self._temporal.reset()
-        out = self._temporal.accumulate(self.primary, self.slot_to_id, self.gen.normals, material, self.w, self.h,
-                                        _temporal.world_to_screen(self.cam, self.w, self.h), self._subpixel, image,
-                                        pixels=pixels, image_out=image_out, triangles=self._triangles,
-                                        vertices=self._vertices, prev_vertices=prev, sigma_plane=sigma_plane, **settings)
-        self._motion_from, self._temporal_tris = None, material.numel()
+            acc.reset()
+        out = acc.accumulate(self.primary, self.slot_to_id, self.gen.normals, material, self.w, self.h,
+                             _temporal.world_to_screen(self.cam, self.w, self.h), self._subpixel, image,
+                             pixels=pixels, image_out=image_out, triangles=self._triangles,
+                             vertices=self._vertices, prev_vertices=prev, sigma_plane=sigma_plane, **settings)
+        self._motion_from, self._temporal_tris, self._accumulated_by = None, material.numel(), acc
         return out
+
+    def svgf(self, image: torch.Tensor, pixels: torch.Tensor | None = None, image_out: torch.Tensor | None = None,
+             sigma_plane: float | None = None, reset: bool = False, **settings):
+        """Variance-guided filtering (mrt.svgf.SvgfAccumulator) of a RAY_PATH frame's float
+        image, called after the frame's last update_result(pixels, image=image) in place of
+        accumulate and denoise: the frame is accumulated as accumulate does, with the moments of
+        its luminance beside the colour, and then filtered with a colour weight that follows each
+        pixel's variance. The result goes to pixels (w*h ABGR int32) and / or image_out (float32
+        [w*h, 4], not `image` itself); returns (pixels, image_out). settings: accumulate's
+        max_history and normal_cos, SvgfAccumulator.filter's iterations, sigma_luminance,
+        normal_squarings and variance_out, and variant, which both take. sigma_plane and the
+        restarts are accumulate's; the two share the vertices set_vertices keeps, and a frame
+        after one that the other accumulated starts a new history. It takes no stream: it runs on
+        torch's current stream, so to use a side stream s call it under `with torch.cuda.stream(s)`.
+        Nothing waits on the host."""
+        self._check_accumulable("svgf")
+        unknown = set(settings) - {"max_history", "normal_cos", "variant", "iterations", "sigma_luminance", "normal_squarings",
+                                   "variance_out"}
+        if unknown:
+            raise _lib.MrtError(f"Renderer.svgf: unknown settings {sorted(unknown)}")
+        if self._svgf is None:
+            self._svgf = _svgf.SvgfAccumulator(self.gen.device)
+        n = self.w * self.h
+        if self._svgf_image is None or self._svgf_image.numel() != 4 * n:
+            self._svgf_image = torch.empty((n, 4), dtype=torch.float32, device=self.gen.device)
+        if sigma_plane is None:
+            sigma_plane = self._default_sigma_plane(_temporal.SIGMA_PLANE_FRACTION_DEFAULT)
+        blend = {k: settings[k] for k in ("max_history", "normal_cos", "variant") if k in settings}
+        self._accumulate_with(self._svgf, image, None, self._svgf_image, sigma_plane, reset, blend)
+        rest = {k: settings[k] for k in ("iterations", "sigma_luminance", "normal_squarings", "variance_out", "variant")
+                if k in settings}
+        return self._svgf.filter(self._svgf_image, pixels=pixels, image_out=image_out, sigma_plane=sigma_plane, **rest)
 
     def batches(self):
         """Every batch of the frame (generated, not traced) as (RayBuffer, first ray) pairs."""

@@ -78,12 +78,15 @@ class TemporalAccumulator:
         if w < 1 or h < 1 or w * h > _lib.MRT_TEMPORAL_MAX_PIXELS:
             raise _lib.MrtError(f"an accumulated frame has 1 .. {_lib.MRT_TEMPORAL_MAX_PIXELS} pixels")
         n = w * h
-        self.sets = [{"guide": torch.empty((n, 8), dtype=torch.float32, device=self.device),
-                      "albedo": torch.empty((n, 4), dtype=torch.float32, device=self.device),
-                      "history": torch.empty((n, 4), dtype=torch.float32, device=self.device)} for _ in range(2)]
+        self.sets = [self._new_set(n) for _ in range(2)]
         self.prev_position = None
         self.w, self.h = w, h
         self._have_prev = False      # another frame size starts over
+
+    def _new_set(self, n: int) -> dict:
+        return {"guide": torch.empty((n, 8), dtype=torch.float32, device=self.device),
+                "albedo": torch.empty((n, 4), dtype=torch.float32, device=self.device),
+                "history": torch.empty((n, 4), dtype=torch.float32, device=self.device)}
 
     @property
     def current(self) -> dict:
@@ -145,7 +148,7 @@ class TemporalAccumulator:
                                                     self.prev_position.data_ptr(), s))
         if pixels is None and image_out is None:
             pixels = torch.zeros(n, dtype=torch.int32, device=self.device)
-        p = _lib.TemporalParams()
+        p = self._params()
         p.width, p.height, p.havePrev, p.maxHistory = w, h, int(self._have_prev), int(max_history)
         p.normalCos, p.sigmaPlane, p.variant = float(normal_cos), float(sigma_plane), int(variant)
         for i in range(16):
@@ -157,11 +160,17 @@ class TemporalAccumulator:
         p.history = cur["history"].data_ptr()
         p.imageOut = None if image_out is None else image_out.data_ptr()
         p.pixels = None if pixels is None else pixels.data_ptr()
-        _lib.check(self.lib.mrt_temporal_accumulate(C.byref(p), s))
+        self._launch(p, cur, prev, s)
         self._cur = 1 - self._cur
         self._have_prev = True
         self._prev_matrix, self._prev_subpixel = m.copy(), (float(subpixel[0]), float(subpixel[1]))
         return pixels, image_out
+
+    _params = _lib.TemporalParams    # what _launch takes: a subclass that carries more per pixel has more fields
+
+    def _launch(self, p, cur: dict, prev: dict, s) -> None:
+        """The frame's last launch, from the filled parameters and the two sets, on stream s."""
+        _lib.check(self.lib.mrt_temporal_accumulate(C.byref(p), s))
 
     def history_length(self) -> torch.Tensor:
         """The current history's length per pixel (float32 [w*h]): a view of its w plane."""

@@ -315,6 +315,57 @@ typedef struct mrth_temporal_params {
 } mrth_temporal_params;
 int  mrth_temporal_accumulate(const mrth_temporal_params* params);
 
+/* The CPU statements of mrt_svgf_accumulate and mrt_svgf_filter (mrt_svgf.h, which states the
+ * arithmetic and the checks), with the same arguments over HOST memory and no stream, built from
+ * the same header (csrc/svgf_common.hpp) and the same plans: the same bits in every output. The
+ * structs are mrt_svgf_accumulate_params and mrt_svgf_filter_params, field for field. Where
+ * mrt_svgf.h says MRT_ERR_INVALID_ARG or MRT_ERR_TOO_LARGE these return MRTH_ERR_INVALID_ARG;
+ * alignment and overlap, which matter to the device's 16-byte accesses and parallel lanes only, are
+ * not checked here. */
+typedef struct mrth_svgf_accumulate_params {
+    int32_t width;
+    int32_t height;
+    int32_t havePrev;
+    int32_t maxHistory;
+    float normalCos;
+    float sigmaPlane;
+    int32_t variant;             /* checked, otherwise ignored: the host has one statement */
+    int32_t reserved;
+    float prevWorldToScreen[16];
+    float prevSubpixel[2];
+    const float* image;
+    const void* guide;
+    const float* albedo;
+    const float* prevPosition;
+    const void* prevGuide;
+    const float* prevHistory;
+    float* history;
+    float* imageOut;
+    uint32_t* pixels;
+    const float* prevMoments;
+    float* moments;
+} mrth_svgf_accumulate_params;
+int  mrth_svgf_accumulate(const mrth_svgf_accumulate_params* params);
+typedef struct mrth_svgf_filter_params {
+    int32_t width;
+    int32_t height;
+    int32_t iterations;
+    int32_t normalSquarings;
+    float sigmaLuminance;
+    float sigmaPlane;
+    int32_t variant;             /* checked, otherwise ignored */
+    int32_t reserved;
+    const float* image;
+    const void* guide;
+    const float* albedo;
+    const float* moments;
+    float* scratch[3];
+    float* imageOut;
+    uint32_t* pixels;
+    float* varianceOut;
+} mrth_svgf_filter_params;
+int  mrth_svgf_filter(const mrth_svgf_filter_params* params);
+
 /* RayBuffer::mortonSort (RayBuffer.cc:256-324): the CPU statement of mrt_ray_sort (mrt.h, which
  * states the key and the order), with the same arguments over HOST memory and no stream. outBox
  * is six host floats (lo.xyz, hi.xyz). The box and the keys are csrc/raysort_common.hpp's on both

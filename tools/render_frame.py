@@ -25,8 +25,9 @@ the edge-avoiding wavelet denoiser (Renderer.denoise; --denoise-iterations, --si
 --sigma-plane: default a fraction of the scene box's diagonal) before it is written; without it the
 file is what it always was. --accumulate N renders N path frames of the camera with the renderer's
 consecutive seeds, blends each into the history of those before it (Renderer.accumulate) and writes
-the last; with --denoise the filter runs after the accumulation. The counts and the rate are the
-last frame's.
+the last; with --denoise the filter runs after the accumulation. --svgf N renders N path frames the
+same way and runs the variance-guided filter on each (Renderer.svgf; --svgf-iterations,
+--sigma-luminance, --sigma-plane) in place of both. The counts and the rate are the last frame's.
 """
 from __future__ import annotations
 
@@ -72,6 +73,10 @@ def main() -> int:
     ap.add_argument("--sigma-plane", type=float, default=None, help="path, --denoise: plane-distance sigma in scene units")
     ap.add_argument("--accumulate", type=int, default=0, metavar="N",
                     help="path: render N frames and write their temporal accumulation (Renderer.accumulate)")
+    ap.add_argument("--svgf", type=int, default=0, metavar="N",
+                    help="path: render N frames through the variance-guided filter (Renderer.svgf) and write the last")
+    ap.add_argument("--svgf-iterations", type=int, default=None, help="path, --svgf: a-trous iterations (0..8)")
+    ap.add_argument("--sigma-luminance", type=float, default=None, help="path, --svgf: luminance sigma in standard deviations")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--out", default="gpurun_out/frame.ppm")
@@ -82,6 +87,10 @@ def main() -> int:
         ap.error("--accumulate accumulates --ray-type path frames")
     if a.accumulate < 0:
         ap.error("--accumulate takes a number of frames")
+    if a.svgf and (a.ray_type != "path" or a.accumulate or a.denoise):
+        ap.error("--svgf filters --ray-type path frames, in place of --accumulate and --denoise")
+    if a.svgf < 0:
+        ap.error("--svgf takes a number of frames")
     if not torch.cuda.is_available():
         raise SystemExit("render_frame needs a GPU")
     scene = mrt.Scene.from_obj(a.obj) if a.obj else mrt.Scene.synthetic(a.scene, 0, 1)
@@ -103,9 +112,10 @@ def main() -> int:
     r.set_params(rt, 1 if rt == RAY_PRIMARY else a.samples, ao_radius, light_pos=light or (0.0, 0.0, 0.0),
                  light_radius=light_radius or 0.0, depth=a.depth, light_color=a.light_color, sky=a.sky, compact=a.compact)
     pixels = torch.zeros(w * h, dtype=torch.int32, device="cuda")
-    image = torch.zeros((w * h, 4), dtype=torch.float32, device="cuda") if a.denoise or a.accumulate else None
+    image = torch.zeros((w * h, 4), dtype=torch.float32, device="cuda") if a.denoise or a.accumulate or a.svgf else None
     blended = torch.zeros((w * h, 4), dtype=torch.float32, device="cuda") if a.denoise and a.accumulate else None
-    for _ in range(max(a.accumulate, 1)):
+    svgf = {k: v for k, v in (("iterations", a.svgf_iterations), ("sigma_luminance", a.sigma_luminance)) if v is not None}
+    for _ in range(max(a.accumulate, a.svgf, 1)):
         r.begin_frame(cam, w, h)
         counted = r.total_num_rays()
         ms, batches, live = 0.0, 0, None
@@ -116,6 +126,8 @@ def main() -> int:
             live = list(r.path_stats) if rt == RAY_PATH else None
         if a.accumulate:
             r.accumulate(image, pixels=pixels, image_out=blended)
+        if a.svgf:
+            r.svgf(image, pixels=pixels, sigma_plane=a.sigma_plane, **svgf)
     if a.denoise:
         settings = {k: v for k, v in (("iterations", a.denoise_iterations), ("sigma_color", a.sigma_color)) if v is not None}
         r.denoise(blended if a.accumulate else image, pixels=pixels, sigma_plane=a.sigma_plane, **settings)
@@ -126,7 +138,7 @@ def main() -> int:
                       "samples": r.num_samples, "light": light, "light_radius": light_radius, "batches": batches,
                       **({"depth": a.depth, "compact": r.compact, "live_last_batch": live} if rt == RAY_PATH else {}),
                       **({"denoised": True} if a.denoise else {}),
-                      **({"accumulated": a.accumulate} if a.accumulate else {}), "trace_ms": round(ms, 4), "rays_counted": counted,
+                      **({"accumulated": a.accumulate} if a.accumulate else {}), **({"svgf": a.svgf} if a.svgf else {}), "trace_ms": round(ms, 4), "rays_counted": counted,
                       "mrays_per_s": round(counted / ms / 1e3, 2) if ms > 0 else None, "image": a.out}))
     return 0
 
